@@ -26,6 +26,13 @@ Multi-GPU: one process per GPU (torch.distributed.run); the only collectives
 are the timing barrier, the max of the times and the sum of the bytes.
 --backend gloo runs the ranks' collectives on the CPU, so N ranks can share
 one GPU (a test of the multi-rank path on a one-GPU box).
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the line with the headline figure.  `--full` adds everything
+else: the round-trip check of every batch, the per-kernel event pass with the
+roofline, the device copy rate, PMC traffic, the config-2 secondary and the
+cpu_baseline leg.  `--dump-outputs DIR` writes what the last timed step
+computed (see dump_outputs).
 """
 import argparse
 import json
@@ -49,6 +56,9 @@ CONFIG_NAMES = {
 }
 CPU_SAMPLE = 1 << 20  # strings of the cpu_baseline sample (bounded CPU work)
 BATCH_SEED_STEP = 104729  # seed offset of rotated batch b (--batches)
+DUMP_SEED = 0x5EEDD0  # --dump-outputs: the sample of strings
+DUMP_STRINGS = 1 << 18  # at most this many sampled strings (5 float64 arrays of them)
+DUMP_BYTES = 5 * 10 ** 6  # at most this many sampled bytes per pool (float32)
 
 
 def parse():
@@ -60,9 +70,17 @@ def parse():
                     help="default: 3 on one GPU, 4 (16M sharded) on more")
     ap.add_argument("--strings", type=int, default=None,
                     help="strings per GPU (configs 2/3/5) or in total (config 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the round trips and measure everything beside the "
+                         "headline figure: per-kernel times and roofline, copy rate, the "
+                         "config-2 secondary, the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them computed to "
+                         "DIR/<name>.npy (a fixed, seeded sample of the strings)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="config 3: skip the config-2 secondary measurement")
+                    help="--full, config 3: skip the config-2 secondary measurement")
     ap.add_argument("--batches", type=int, default=3,
                     help="configs 2/3: distinct input batches rotated over the steps (step i "
                          "encodes batch i %% B), so no step re-reads the raw input the step "
@@ -79,9 +97,13 @@ def parse():
     ap.add_argument("--backend", default="auto", choices=["auto", "nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (auto: nccl = RCCL)")
     ap.add_argument("--dump-dir", default=None,
-                    help="(tests) each rank writes its shard bounds, encoded pool, offsets and "
-                         "decode status there after the warm-up, for an outside check")
-    return ap.parse_args()
+                    help="(tests, with --full) each rank writes its shard bounds, encoded pool, "
+                         "offsets and decode status there after the round-trip check, for an "
+                         "outside check")
+    args = ap.parse_args()
+    if args.dump_dir and not args.full:
+        ap.error("--dump-dir writes what the round-trip check of --full leaves")
+    return args
 
 
 def cpu_info():
@@ -258,17 +280,17 @@ def main():
                  % (nb, len(off) - 1, int(off[-1])))
         out, ctx = run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce,
                                  [(b[0], b[1]) for b in batches], cfg, scaling, data)
-        if cfg == 3 and not args.no_secondary:
+        if args.full and cfg == 3 and not args.no_secondary:
             b2 = [gen(2, rank, b)[:2] for b in range(nb)]
             sec, _ = run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce,
                                    b2, 2, "weak", "", host_resident=False,
-                                   min_window_ms=args.secondary_ms)
+                                   min_window_ms=args.secondary_ms, dump=False)
             out["secondary"] = {"config2": {k: sec[k] for k in ("value", "ms_per_step", "steps")}}
             out["secondary"]["config2"].update(
                 timed_ms=round(sec["ms_per_step"] * sec["steps"], 2),
                 workload=CONFIG_NAMES[2], strings_per_gpu=sec["config"]["strings_per_gpu"],
                 raw_bytes_per_gpu=sec["config"]["raw_bytes_per_gpu"], roofline=sec["roofline"])
-        if rank == 0 and not args.no_cpu_baseline and world == 1:
+        if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
             progress("cpu baseline")
             info = cpu_info()
             threads = args.cpu_threads or info["usable"]
@@ -303,15 +325,58 @@ def main():
 # steps, right before the timed steps: at the driver's 20 steps (6 ms) the
 # launch times and the timed window sit partly in the GPU's clock ramp
 # (round 5: decode launch 0.231 ms at 20 event steps vs 0.220 at 100); the
-# timed region is still exactly --steps steps.
+# timed region is still exactly --steps steps.  A plain run (no --full)
+# runs the same steps without the events, so its timed window sits at the
+# same clocks as --full's (`ramp_steps` in the line).
 EVENT_STEPS_MIN = 100
 
 
+def dump_outputs(torch, dirpath, world, n, enc, enc_off, dec, dec_off, status):
+    """--dump-outputs: what the caller of the timed path receives from its
+    last step, as float .npy files under dirpath, for comparing two builds
+    output for output.  The pools are hundreds of MB, so the files hold a
+    fixed sample: the first DUMP_STRINGS strings of a permutation seeded with
+    DUMP_SEED (`strings.npy`), for each of them its encoded offset and length
+    (`enc_off.npy`, `enc_len.npy`; not for the decode-only config), its output
+    slot and decode status (`dec_off.npy`, `status.npy`), all float64 (exact);
+    and of the leading sampled strings, as many as fit DUMP_BYTES bytes, every
+    encoded byte and every decoded byte in that order (`enc_bytes.npy`,
+    `dec_bytes.npy`, float32).  About 50 MB at most.  With N > 1 ranks the
+    names carry a `rank<r>_` prefix."""
+    os.makedirs(dirpath, exist_ok=True)
+    pre = "rank%d_" % int(os.environ.get("RANK", "0")) if world > 1 else ""
+    sel = np.random.Generator(np.random.PCG64(DUMP_SEED)).permutation(n)[:DUMP_STRINGS]
+
+    def save(name, a, dt):
+        np.save(os.path.join(dirpath, pre + name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+    def sample_bytes(pool, start, ln):
+        """the bytes pool[start[i] : start[i] + ln[i]] of the leading sampled
+        strings whose total stays within DUMP_BYTES, gathered on the device"""
+        k = int(np.searchsorted(np.cumsum(ln), DUMP_BYTES, side="right"))
+        start, ln = start[:k], ln[:k]
+        idx = np.repeat(start, ln) + (np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln))
+        return pool[torch.from_numpy(idx).to(pool.device)].cpu().numpy()
+
+    save("strings", sel, np.float64)
+    if enc is not None:
+        eo = enc_off[:n + 1].cpu().numpy().view(np.uint32).astype(np.int64)
+        save("enc_off", eo[sel], np.float64)
+        save("enc_len", eo[sel + 1] - eo[sel], np.float64)
+        save("enc_bytes", sample_bytes(enc, eo[sel], eo[sel + 1] - eo[sel]), np.float32)
+    do = dec_off[:n + 1].cpu().numpy().view(np.uint32).astype(np.int64)
+    st = status[:n].cpu().numpy().astype(np.int64)
+    save("dec_off", do[sel], np.float64)
+    save("status", st[sel], np.float64)
+    save("dec_bytes", sample_bytes(dec, do[sel], np.maximum(st[sel], 0)), np.float32)
+
+
 def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches, cfg,
-                  scaling, data, host_resident=None, min_window_ms=0.0):
+                  scaling, data, host_resident=None, min_window_ms=0.0, dump=True):
     """batches: [(pool, off)] rotated over the steps (step i encodes batch
-    i % len(batches)); min_window_ms > 0 (the secondary): time more than
-    --steps steps if that is needed for a timed window at least that long."""
+    i % len(batches)); min_window_ms > 0 (the secondary, --full): time more than
+    --steps steps if that is needed for a timed window at least that long;
+    dump: this is the run --dump-outputs writes."""
     nb = len(batches)
     srcs, srcs_off, raws, ns, enc_totals = [], [], [], [], []
     codec0 = nghttp2_amd.HuffmanBatchCodec(dev)
@@ -373,9 +438,10 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
     pipes = [Pipe(torch.cuda.current_stream() if k == 0 else torch.cuda.Stream(device=dev))
              for k in range(max(1, args.streams))]
     P0 = pipes[0]
+    full = args.full
     KE = max(args.steps, EVENT_STEPS_MIN)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True),
-           torch.cuda.Event(enable_timing=True)) for _ in range(KE)]
+           torch.cuda.Event(enable_timing=True)) if full else None for _ in range(KE)]
 
     for w in range(args.warmup):
         for k, p in enumerate(pipes):
@@ -383,10 +449,10 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
         torch.cuda.synchronize()
         progress("config %d: warm-up step %d" % (cfg, w))
 
-    progress("config %d: warm-up done, checking the round trips" % cfg)
-    # correctness gate on every batch of this rank (fails loudly, never
+    progress("config %d: warm-up done%s" % (cfg, ", checking the round trips" if full else ""))
+    # correctness gate on every batch of this rank (--full; fails loudly, never
     # measured); batch 0 last, so P0 holds it for --dump-dir
-    for b in reversed(range(nb)):
+    for b in reversed(range(nb)) if full else ():
         for p in pipes:
             p.run(b)
         torch.cuda.synchronize()
@@ -399,9 +465,9 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
             "decode(encode(x)) length mismatch"
         assert int(P0.enc_off[k].item()) & 0xFFFFFFFF == enc_totals[b]
         verify_roundtrip(P0.dec, P0.dec_off[:k + 1].cpu().numpy().view(np.uint32), *batches[b])
-    st = P0.status[:n].cpu().numpy()
     raw_len = np.diff(off.astype(np.int64))
     if args.dump_dir:
+        st = P0.status[:n].cpu().numpy()
         rk = int(os.environ.get("RANK", "0"))
         np.savez(os.path.join(args.dump_dir, "rank%d.npz" % rk), data=np.array(data),
                  enc=P0.enc[:enc_total].cpu().numpy(),
@@ -409,17 +475,19 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
                  dec=P0.dec[:int(P0.dec_off[n].item()) & 0xFFFFFFFF].cpu().numpy(),
                  dec_off=P0.dec_off[:n + 1].cpu().numpy().view(np.uint32))
 
-    progress("config %d: round trips checked, timing" % cfg)
-    # per-kernel timing (roofline): K plain steps with events on the stream
+    progress("config %d: %stiming" % (cfg, "round trips checked, " if full else ""))
+    # per-kernel timing (--full, roofline): K plain steps with events on the
+    # stream; a plain run: the same steps without events (the clock ramp)
     for i in range(KE):
         P0.run(i % nb, ev[i])
     torch.cuda.synchronize()
-    t_enc = np.mean([ev[i][0].elapsed_time(ev[i][1]) for i in range(KE)]) * 1e-3
-    t_dec = np.mean([ev[i][1].elapsed_time(ev[i][2]) for i in range(KE)]) * 1e-3
 
     steps = args.steps
-    if min_window_ms > 0:  # (the two-stream step is shorter than enc + dec)
-        steps = max(steps, int(np.ceil(min_window_ms / (0.7 * (t_enc + t_dec) * 1e3))))
+    if full:
+        t_enc = np.mean([ev[i][0].elapsed_time(ev[i][1]) for i in range(KE)]) * 1e-3
+        t_dec = np.mean([ev[i][1].elapsed_time(ev[i][2]) for i in range(KE)]) * 1e-3
+        if min_window_ms > 0:  # (the two-stream step is shorter than enc + dec)
+            steps = max(steps, int(np.ceil(min_window_ms / (0.7 * (t_enc + t_dec) * 1e3))))
 
     # the timed steps: plain launches on the streams (no events in between)
     if world > 1:
@@ -432,6 +500,13 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    if dump and args.dump_outputs and steps > 0:
+        # the buffers of the pipe that ran the last timed step hold its outputs
+        pl, kl = pipes[(steps - 1) % len(pipes)], ns[(steps - 1) % nb]
+        dump_outputs(torch, args.dump_outputs, world, kl, pl.enc, pl.enc_off, pl.dec,
+                     pl.dec_off, pl.status)
+        progress("config %d: outputs of the last timed step written" % cfg)
 
     B_b = [2 * r + 2 * e + 24 * k for r, e, k in zip(raws, enc_totals, ns)]
     B_rank = sum(B_b[i % nb] for i in range(steps))  # all the timed steps
@@ -451,26 +526,28 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
     # same config (profiles/traffic.json, FETCH_SIZE x 2 + WRITE_SIZE per
     # MI355X_MICROARCH.md), when recorded for this batch size.
     # (per launch: the event pass's mean over the rotated batches)
-    alg = [r + e + 12 * k for r, e, k in zip(raws, enc_totals, ns)]  # reads E + offsets, writes R + status
-    dec_alg = int(round(np.mean([alg[i % nb] for i in range(KE)])))
-    enc_alg = dec_alg
-    achieved = dec_alg / t_dec / 1e9
-    copy_gbs = device_copy_gbs(torch, dev)
-    roof = {"bound": "hbm", "kernel": "k_decode_items", "achieved": round(achieved, 2),
-            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": traffic_for(cfg, n, "k_decode_items"), "alg_bytes_per_launch": dec_alg,
-            "launch_ms": round(t_dec * 1e3, 4), "event_steps": KE, "enc_ms": round(t_enc * 1e3, 4),
-            "enc_achieved": round(enc_alg / t_enc / 1e9, 2),
-            # secondary roofline: the device-to-device copy rate
-            # measured here, the attainable HBM ceiling for a streaming kernel
-            "copy_peak": round(copy_gbs, 1), "frac_vs_copy": round(achieved / copy_gbs, 5)}
-    if cfg == 2:
-        roof["note"] = ("config 2's working set per step (~118 MB) fits the 256 MiB Infinity "
-                        "Cache: its GB/s and frac are partly cache-served, not pure HBM")
+    roof = None
+    if full:
+        alg = [r + e + 12 * k for r, e, k in zip(raws, enc_totals, ns)]  # reads E + offsets, writes R + status
+        dec_alg = int(round(np.mean([alg[i % nb] for i in range(KE)])))
+        enc_alg = dec_alg
+        achieved = dec_alg / t_dec / 1e9
+        copy_gbs = device_copy_gbs(torch, dev)
+        roof = {"bound": "hbm", "kernel": "k_decode_items", "achieved": round(achieved, 2),
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "traffic": traffic_for(cfg, n, "k_decode_items"), "alg_bytes_per_launch": dec_alg,
+                "launch_ms": round(t_dec * 1e3, 4), "event_steps": KE, "enc_ms": round(t_enc * 1e3, 4),
+                "enc_achieved": round(enc_alg / t_enc / 1e9, 2),
+                # secondary roofline: the device-to-device copy rate
+                # measured here, the attainable HBM ceiling for a streaming kernel
+                "copy_peak": round(copy_gbs, 1), "frac_vs_copy": round(achieved / copy_gbs, 5)}
+        if cfg == 2:
+            roof["note"] = ("config 2's working set per step (~118 MB) fits the 256 MiB Infinity "
+                            "Cache: its GB/s and frac are partly cache-served, not pure HBM")
 
     out = {"metric": "GB/s HPACK Huffman enc+dec (device-resident, batched headers)",
            "value": round(value, 3), "unit": "GB/s", "n_gpus": world,
-           "steps": steps, "warmup": args.warmup,
+           "steps": steps, "warmup": args.warmup, "ramp_steps": KE, "full": full,
            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
            "scaling": scaling, "vs_baseline": None, "dtype": "u8",
            "data": "synthetic (%s)" % data,
@@ -479,8 +556,9 @@ def run_roundtrip(args, torch, dist, nghttp2_amd, dev, world, allreduce, batches
                       "E_over_R": round(enc_total / max(1, raw_bytes), 4),
                       "alg_bytes_per_step_all_gpus": int(round(B_total / steps)),
                       "parallelism": "shard%d (independent batches, no collective)" % world,
-                      "streams": len(pipes), "batches": nb},
-           "roofline": roof}
+                      "streams": len(pipes), "batches": nb}}
+    if full:
+        out["roofline"] = roof
 
     if host_resident is None:
         host_resident = args.host_resident
@@ -632,19 +710,24 @@ def run_decode_only(args, torch, dist, nghttp2_amd, W, dev, world, rank, allredu
         for p in pipes:
             run(p)
     torch.cuda.synchronize()
+    full = args.full
     st = pipes[0][3].cpu().numpy()
-    valid = np.isin(cats, [0, 5, 6])
-    assert np.array_equal(st[valid], nsym[valid]), "valid adversarial strings mis-decoded"
-    assert (st[np.isin(cats, [1, 2])] == -523).all(), "EOS / long padding not rejected"
+    if full:
+        valid = np.isin(cats, [0, 5, 6])
+        assert np.array_equal(st[valid], nsym[valid]), "valid adversarial strings mis-decoded"
+        assert (st[np.isin(cats, [1, 2])] == -523).all(), "EOS / long padding not rejected"
     written = int(np.maximum(st, 0).sum())
+    # (--full: the event pass; a plain run: the same steps without events)
     KE = max(args.steps, EVENT_STEPS_MIN)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(KE)]
+          for _ in range(KE if full else 0)]
     s0 = pipes[0][0]
     for i in range(KE):
-        ev[i][0].record(s0)
+        if full:
+            ev[i][0].record(s0)
         run(pipes[0])
-        ev[i][1].record(s0)
+        if full:
+            ev[i][1].record(s0)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -655,17 +738,19 @@ def run_decode_only(args, torch, dist, nghttp2_amd, W, dev, world, rank, allredu
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and args.steps > 0:
+        _, dst_l, doff_l, st_l = pipes[(args.steps - 1) % len(pipes)]
+        dump_outputs(torch, args.dump_outputs, world, n, None, None, dst_l, doff_l, st_l)
     B_rank = E + written + 12 * n
     if world > 1:
         elapsed = allreduce(elapsed, dist.ReduceOp.MAX)
         B_total = allreduce(B_rank, dist.ReduceOp.SUM)
     else:
         B_total = float(B_rank)
-    t_dec = np.mean([a.elapsed_time(b) for a, b in ev]) * 1e-3
-    achieved = B_rank / t_dec / 1e9
     out = {"metric": "GB/s HPACK Huffman decode (device-resident, adversarial batch)",
            "value": round(B_total * args.steps / elapsed / 1e9, 3), "unit": "GB/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ramp_steps": KE, "full": full,
            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
            "data": "synthetic (gen_adversarial, seed 0x%X + 7919*rank)" % W.SEED[5],
@@ -673,13 +758,17 @@ def run_decode_only(args, torch, dist, nghttp2_amd, W, dev, world, rank, allredu
                       "enc_bytes_per_gpu": E, "decoded_bytes_per_gpu": written,
                       "failing_strings": int((st < 0).sum()),
                       "parallelism": "shard%d (independent batches, no collective)" % world,
-                      "streams": len(pipes)},
-           "roofline": {"bound": "hbm", "kernel": "k_decode_items", "achieved": round(achieved, 2),
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 5),
-                        "traffic": traffic_for(5, n, "k_decode_items"),
-                        "alg_bytes_per_launch": B_rank, "launch_ms": round(t_dec * 1e3, 4),
-                        "event_steps": KE}}
+                      "streams": len(pipes)}}
+    if not full:
+        return out
+    t_dec = np.mean([a.elapsed_time(b) for a, b in ev]) * 1e-3
+    achieved = B_rank / t_dec / 1e9
+    out["roofline"] = {"bound": "hbm", "kernel": "k_decode_items", "achieved": round(achieved, 2),
+                       "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 5),
+                       "traffic": traffic_for(5, n, "k_decode_items"),
+                       "alg_bytes_per_launch": B_rank, "launch_ms": round(t_dec * 1e3, 4),
+                       "event_steps": KE}
     copy_gbs = device_copy_gbs(torch, dev)
     out["roofline"].update(copy_peak=round(copy_gbs, 1),
                            frac_vs_copy=round(achieved / copy_gbs, 5))

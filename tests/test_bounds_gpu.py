@@ -93,6 +93,10 @@ def test_bounds_lib_built_and_exports():
     report; the product's report says it compiled no checks (1), without a
     GPU call."""
     assert os.path.exists(BOUNDS_LIB), "build() makes " + BOUNDS_LIB
+    # torch first, as nghttp2_amd.lib() loads it: loaded before torch, the
+    # library would bind a second HIP runtime, and the GPU tests that run
+    # later in this process would find no device through it
+    import torch  # noqa: F401
     for path, want in ((BOUNDS_LIB, None), (os.path.join(REPO, "nghttp2_amd", "lib",
                                                          "libnghttp2_amd_hd.so"), 1)):
         L = ctypes.CDLL(path)

@@ -356,7 +356,7 @@ def _bench_ranks_gloo_one_gpu(nranks, total, tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", str(nranks), "--backend", "gloo",
            "--config", "4", "--strings", str(total), "--steps", "3", "--warmup", "1",
-           "--streams", "1", "--no-cpu-baseline", "--dump-dir", str(tmp_path)]
+           "--streams", "1", "--full", "--no-cpu-baseline", "--dump-dir", str(tmp_path)]
     # (rank 0's progress lines pass through to the test's output: a long run
     # keeps printing)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=540, env=env, cwd=REPO)

@@ -20,8 +20,8 @@ for s in $STEPS; do
   case $s in
     pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v -rf --timeout 120 --timeout-method thread ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench 600 python bench.py ${BENCH_ARGS:-} ;;
-    bench3) run bench3 600 python bench.py --config 3 --no-cpu-baseline ;;
+    bench)  run bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
+    bench3) run bench3 600 python bench.py --full --config 3 --no-cpu-baseline ;;
     prof)   run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run \
               --output-format csv -- python3 bench.py --no-cpu-baseline ${BENCH_ARGS:-} ;;
   esac

@@ -20,9 +20,9 @@ for s in ${STEPS:-pytest smoke bench bench3 host prof pmc names}; do
   case $s in
     pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -v -rf --timeout 120 --timeout-method thread ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench 600 python bench.py ;;
-    bench3) run bench3 600 python bench.py --config 3 --no-cpu-baseline ;;
-    host)   run bench_host 600 python bench.py --host-resident --no-cpu-baseline ;;
+    bench)  run bench 600 python bench.py --full ;;
+    bench3) run bench3 600 python bench.py --full --config 3 --no-cpu-baseline ;;
+    host)   run bench_host 600 python bench.py --full --host-resident --no-cpu-baseline ;;
     prof)   rm -rf $O/prof2 $O/prof3 $O/prof2s1 $O/prof3s1
             # --streams 1: launches never overlap, so the per-kernel averages
             # are the isolated durations the roofline uses
