@@ -131,6 +131,26 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t v) {  // uniform result
   return __builtin_amdgcn_readlane(v, 63);
 }
 
+// A wave's LDS accesses before this point are complete and visible to all of
+// its lanes after it (release fence, wave barrier, acquire fence): the
+// hand-over between lanes of one wave through LDS, no workgroup barrier.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// s_waitcnt takes its counters as one immediate whose layout is the device
+// family's.  gfx9 (gfx950 included): vmcnt in bits 3:0 and 15:14, expcnt in
+// 6:4, lgkmcnt in 11:8; a field of all ones does not wait.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "wait_vmcnt0 / wait_lgkmcnt0 encode s_waitcnt for gfx9-family devices"
+#endif
+// vmcnt(0): every global load and store of the wave has completed
+__device__ __forceinline__ void wait_vmcnt0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// lgkmcnt(0): every LDS (and scalar memory) access of the wave has completed
+__device__ __forceinline__ void wait_lgkmcnt0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+
 // Exclusive scan across a workgroup of NT threads (NT/64 words of `sm`).
 template <int NT>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *sm,
@@ -304,17 +324,11 @@ __global__ __launch_bounds__(WG) void k_scan_apply(uint32_t *__restrict__ offs, 
 }
 
 #define ENC_WAVES 4                  // waves per encode workgroup (tile = 256 strings)
-#ifndef EC_STORE4
-#define EC_STORE4 1  // k_encode: an interior round of <= 256 words as four unconditional stores
-#endif
-#ifndef EC_INTERIOR
-#define EC_INTERIOR 1  // k_encode: interior rounds store their words without edge tests
-#endif
-#ifndef EC_CNT_SPLIT
-#define EC_CNT_SPLIT 1  // the count's in-chunk prefixes in two halves (16-byte lane stride)
-#endif
 #ifndef EC_CNT_UNROLL
-#define EC_CNT_UNROLL 1  // the count's wave loop: two chunk buffers, unrolled by two
+// the count's wave loop: two chunk buffers, unrolled by two.  (Kept as a
+// switch: its other arm, the rolled loop, is the only reader of EC_CNT_PFD,
+// a depth the next A/Bs still override.)
+#define EC_CNT_UNROLL 1
 #endif
 #ifndef EC_CNT_PFD
 #define EC_CNT_PFD 2  // k_enc_count: rounds of chunks in flight per wave (4: no faster)
@@ -379,37 +393,30 @@ __device__ __forceinline__ uint32_t wave_string_bits(const uint8_t *__restrict__
     u32x4 v0, v1;
     v0.x = pk[0]; v0.y = pk[1]; v0.z = pk[2]; v0.w = pk[3];
     v1.x = pk[4]; v1.y = pk[5]; v1.z = pk[6]; v1.w = pk[7];
-#if EC_CNT_SPLIT
     // (the chunk's first and second 8 prefixes in two halves of pr: lane
     // strides of 16 bytes, 4-way per 32 lanes -- the least 16-byte stores
-    // can take -- instead of 32 bytes, 8-way.  Round 6: count 34.9 vs 37.0
-    // us on config 3, 14.4 vs 15.2 on config 2, outputs equal;
+    // can take.  Lost to it: both halves side by side at pr + 8 lane, a
+    // 32-byte stride, 8-way.  Round 6: count 34.9 vs 37.0 us on config 3,
+    // 14.4 vs 15.2 on config 2, outputs equal;
     // profiles/r06/ab/ab_count_split_prefixes.log)
     *(lds_u32x4 *)(pr + 4u * lane) = v0;
     *(lds_u32x4 *)(pr + 256u + 4u * lane) = v1;
-#else
-    *(lds_u32x4 *)(pr + 8u * lane) = v0;
-    *(lds_u32x4 *)(pr + 8u * lane + 4u) = v1;
-#endif
     const uint32_t Sinc = wave_incl_scan(run), Sx = Sinc - run;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // the string ends in this round: P = chunk start + in-chunk prefix
+    // (byte r of the round: u16 r & 7 of chunk r >> 4, in half r & 8)
     const uint32_t ra = a_l - base, rb = b_l - base;
     const uint32_t xa = __shfl(Sx, (ra >> 4) & 63u, 64), xb = __shfl(Sx, (rb >> 4) & 63u, 64);
     if (sl && ra < 1024u) {
-      Pa = Rc + xa + pr16[EC_CNT_SPLIT ? ((ra >> 4) << 3) | (ra & 7u) | ((ra & 8u) << 6) : ra];
+      Pa = Rc + xa + pr16[((ra >> 4) << 3) | (ra & 7u) | ((ra & 8u) << 6)];
       ga = true;
     }
     if (sl && rb < 1024u) {
-      Pb = Rc + xb + pr16[EC_CNT_SPLIT ? ((rb >> 4) << 3) | (rb & 7u) | ((rb & 8u) << 6) : rb];
+      Pb = Rc + xb + pr16[((rb >> 4) << 3) | (rb & 7u) | ((rb & 8u) << 6)];
       gb = true;
     }
     Rc += __builtin_amdgcn_readlane(Sinc, 63);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   };
   // every lane loads (a chunk past the wave's bytes at a clamped index,
   // used as zeros): a load behind a branch that a whole wave may skip makes
@@ -725,11 +732,10 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
   if (threadIdx.x == WG - 1) o_sh[WG] = o_me + E_me;
   __syncthreads();
   if (nstr == 0) return;
-  // the wave's output bytes (EC_STORE4, the pack: as scalars, so the
-  // round's word bounds and path choices stay scalar)
-  const uint32_t OA = EC_STORE4 && !FR ? __builtin_amdgcn_readfirstlane(o_sh[64u * wv]) : o_sh[64u * wv];
-  const uint32_t OZ = EC_STORE4 && !FR ? __builtin_amdgcn_readfirstlane(o_sh[64u * wv + nstr])
-                                       : o_sh[64u * wv + nstr];
+  // the wave's output bytes (the pack: as scalars, so the round's word
+  // bounds and path choices stay scalar)
+  const uint32_t OA = !FR ? __builtin_amdgcn_readfirstlane(o_sh[64u * wv]) : o_sh[64u * wv];
+  const uint32_t OZ = !FR ? __builtin_amdgcn_readfirstlane(o_sh[64u * wv + nstr]) : o_sh[64u * wv + nstr];
   const uint64_t G0 = 8ull * OA;
   const uint32_t pad_l = sl && (!FR || H_me) ? 8u * Eh_me - bits_me : 0u;  // EOS-prefix bits after string l
   const uint32_t olast_l = o_me + E_me - 1u;             // its last output byte (if E > 0)
@@ -761,9 +767,7 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
       if (pfx) atomicAdd((uint32_t *)&pdw[(a_l - 1u - base) >> 1], (8u * PL_me) << (16u * ((a_l - 1u - base) & 1u)));
       if (anyraw) {
         if (lane < 32u) rwm[lane] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const uint32_t lo = max(a_l, base), hi = min(b_l, base + 1024u);
         if (rawl && lo < hi) {
           for (uint32_t w = (lo - base) >> 5; w <= (hi - 1u - base) >> 5; ++w) {
@@ -774,9 +778,7 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
         }
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const uint32_t p0 = base + 16u * lane;
     const bool act = p0 < Z;  // (lanes past the wave's last chunk: nothing)
     const uint32_t wd[4] = {wn.x, wn.y, wn.z, wn.w};
@@ -914,9 +916,7 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
         atomicOr((uint32_t *)&img[(uint32_t)((q >> 2) - WB) + EC_M], v << (24u - 8u * (q & 3u)));
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // ---- store whole words and zero them; carry a partial last word
     const uint32_t xe = last_round ? 8u * (OZ - OA) : x + __builtin_amdgcn_readlane(Sinc, 63) + X0 - RA;
     const uint32_t nw = (uint32_t)(((G0 + xe + 31u) >> 5) - WB);
@@ -928,22 +928,22 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
     uint8_t *const dw = dst + 4ull * WB;  // (uniform)
     HD_CHECK(EC_M + nw <= RW, 0x104u);
     HD_CHECK(ihi <= ilo || 4ull * (WB + ihi) <= dst_cap, 0x105u);
-#if EC_INTERIOR
     // a round whose words all lie inside the wave's output (every round but
     // the first and the last, in practice): whole-word stores with no
     // per-word edge test (its exec-mask branches cost ~6 scalar
-    // instructions per word and lane; round 6: config 3 encode pair 130.3
-    // vs 135.0 us, emit 217.0 vs 223.6, config 2 flat, outputs equal;
+    // instructions per word and lane; lost to it: every round through the
+    // edge-tested loop below.  Round 6: config 3 encode pair 130.3 vs 135.0
+    // us, emit 217.0 vs 223.6, config 2 flat, outputs equal;
     // profiles/r06/ab/ab_pack_interior_rounds.log)
     if (ilo == 0u && ihi >= nst) {
-#if EC_STORE4
-      // (EC_STORE4, the pack: a round of 1..256 words as exactly four store
+      // (the pack: a round of 1..256 words as exactly four store
       // instructions with no branch -- a lane past the round's words stores
       // the last word again, read before any word is cleared; the other
-      // store paths end waiting for their stores.  Config 3 encode pair
+      // store paths end waiting for their stores.  Lost to it: the loop
+      // below for every interior round, no waits.  Config 3 encode pair
       // 120.9 vs 122.9 us, config 2 flat; the string literals' config 2
       // 69.8 vs 68.0, so not for them; profiles/r06/ab/ab_pack_store4.log)
-      if (EC_STORE4 && !FR && nst - 1u < 256u) {
+      if (!FR && nst - 1u < 256u) {
         uint32_t v[4], ix[4];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
@@ -954,21 +954,15 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
         for (uint32_t k = 0; k < 4u; ++k) img[EC_M + ix[k]] = 0u;
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) *reinterpret_cast<uint32_t *>(dw + 4u * ix[k]) = v[k];
-      } else
-#endif
-      {
+      } else {
         for (uint32_t i = lane; i < nst; i += 64u) {
           const uint32_t v = __builtin_bswap32(img[EC_M + i]);
           img[EC_M + i] = 0u;
           *reinterpret_cast<uint32_t *>(dw + 4u * i) = v;
         }
-#if EC_STORE4
-        if (!FR) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this path's stores, counted out
-#endif
+        if (!FR) wait_vmcnt0();  // this path's stores, counted out
       }
-    } else
-#endif
-    {
+    } else {
       for (uint32_t i = lane; i < nst; i += 64u) {
         const uint32_t v = __builtin_bswap32(img[EC_M + i]);
         img[EC_M + i] = 0u;
@@ -982,9 +976,7 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
           }
         }
       }
-#if EC_STORE4
-      if (!FR) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-#endif
+      if (!FR) wait_vmcnt0();
     }
     if (first && lane < EC_M) img[lane] = 0u;  // the bytes before A
     if (!FR) {
@@ -993,22 +985,16 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
       if (tl) pdh[tail_l - base] = 0u;
       if (pfx) pdh[a_l - 1u - base] = 0u;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (!last_round && nst < nw) {  // the partial word moves to img[EC_M]
       const uint32_t cw = img[EC_M + nst];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       if (lane == 0) {
         img[EC_M + nst] = 0u;
         img[EC_M] = cw;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     x = xe;
   }
 }
@@ -1192,27 +1178,18 @@ __device__ __forceinline__ uint32_t long_entry(const TT &T, uint32_t win, uint32
   // zero: win << (n1 + 1), by alignbit so that n1 = 31 gives 0)
   const uint32_t v = T.long1[long_index(win)];
   const uint32_t L = E_USED(v);
-#if DD_SLOWU
-  // (selects, not an early return: no exec-mask branch in the slow path)
-  const bool fits = L <= rem;
-  const uint32_t r = fits ? v & ~E_EOS : v & ~(E_EOS | 0xFFu);
-  return fits && (v & E_EOS) ? 0xFFFFFFFFu : r;
-#else
+  // (A form of this by selects only, with no early return, sat here behind
+  // `#if DD_SLOWU`, a macro defined further down the file: it was never
+  // compiled, and every measurement of the uniform slow branch in dd_run
+  // was taken with this form.)
   if (L <= rem && (v & E_EOS)) return 0xFFFFFFFFu;
   return L <= rem ? v & ~E_EOS : v & ~(E_EOS | 0xFFu);
-#endif
 }
 // The index of a window's code in T.long1 (long_entry's read).
 __device__ __forceinline__ uint32_t long_index(uint32_t win) {
   const uint32_t n1 = min(max((uint32_t)__clz((int)~win), (uint32_t)HD_HUFF_LONG1_N0),
                           (uint32_t)(HD_HUFF_LONG1_N0 + HD_HUFF_LONG1_ROWS - 1));
   return (n1 - HD_HUFF_LONG1_N0) * 32u + (__builtin_amdgcn_alignbit(win, 0u, 31u - n1) >> 27);
-}
-
-// First-level miss: the code is longer than the lookup.
-template <class TT>
-__device__ __forceinline__ uint32_t slow_entry(const TT &T, uint32_t win, uint32_t rem) {
-  return long_entry(T, win, rem);
 }
 
 // Decode from bit bp (positions relative to the staged round) of a string
@@ -1236,7 +1213,7 @@ __device__ __forceinline__ SubOut decode_item(const DecTables &T, const lds_u32 
       const uint32_t w = win_at(ibe, bp);
       const uint32_t rem = bend - bp;
       uint32_t e = T.lut[w >> (32 - HD_HUFF_LUT_BITS)];
-      if (e == 0u) e = slow_entry(T, w, rem);
+      if (e == 0u) e = long_entry(T, w, rem);
       if (e == 0xFFFFFFFFu) {
         r.entry = r.exit = XUNKNOWN;
         return r;
@@ -1262,7 +1239,7 @@ __device__ __forceinline__ SubOut decode_item(const DecTables &T, const lds_u32 
     const uint32_t w = win_q(ibe, q);                            \
     uint32_t e = T.lut[w >> (32 - HD_HUFF_LUT_BITS)];            \
     if (e == 0u) {                                               \
-      e = slow_entry(T, w, 30u);                                 \
+      e = long_entry(T, w, 30u);                                 \
       if (e == 0xFFFFFFFFu) {                                    \
         F = F2 = INT32_MIN;                                      \
         e = 0u;                                                  \
@@ -1290,7 +1267,7 @@ __device__ __forceinline__ SubOut decode_item(const DecTables &T, const lds_u32 
     const uint32_t w = win_at(ibe, bp);
     uint32_t e = T.lut[w >> (32 - HD_HUFF_LUT_BITS)];
     if (e == 0u) {
-      e = slow_entry(T, w, rem);
+      e = long_entry(T, w, rem);
       if (e == 0xFFFFFFFFu) {
         failed = true;
         break;
@@ -1421,9 +1398,7 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
           reinterpret_cast<lds_u32 *>(ibw)[4u * c + 6u] = __builtin_bswap32(v.z);
           reinterpret_cast<lds_u32 *>(ibw)[4u * c + 7u] = __builtin_bswap32(v.w);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
       }
       // the carried exit is a bit position of the previous round's staging
       if (carry_exit < NOSPEC) carry_exit -= 8u * (IB - IB_prev);
@@ -1531,9 +1506,7 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
       carry_exit = __builtin_amdgcn_readlane(r.exit, nv - 1u);
       carry_cnt = __builtin_amdgcn_readlane(seg, nv - 1u);
       // the next round overwrites the staged input
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
   }
 }
@@ -1594,14 +1567,8 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
 #ifndef DD_TAILU
 #define DD_TAILU 2u  // the workgroup's last DD_TAILU x waves units are claimed singly
 #endif
-#ifndef DD_JIT_TAIL
-#define DD_JIT_TAIL 1  // a tail unit is claimed when the wave's task ends, not one task ahead
-#endif
 #ifndef DD_SK40
 #define DD_SK40 2u  // the 40-byte instance serves long codes every 2nd pair (dd_run SLOWK)
-#endif
-#ifndef DD_DIRECT_MODE
-#define DD_DIRECT_MODE 1  // dd_run's direct long codes (SLOWK == 1) when the caller asks: 0 never
 #endif
 #ifndef DD_DIRECT_MIN
 #define DD_DIRECT_MIN 4u  // lanes of a round with long codes that switch the wave's next round to direct
@@ -1609,44 +1576,55 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
 #ifndef DD_DIRECT_KEEP
 #define DD_DIRECT_KEEP 4u  // ... and to keep it on for the round after
 #endif
-#ifndef DD_DPAIR
-#define DD_DPAIR 1  // dd_run: SLOWK 2 as two pairs per loop trip
-#endif
-#ifndef DD_FSTEP
-#define DD_FSTEP 1  // dd_run: fast single steps between the pairs and the careful steps
-#endif
-#ifndef DD_SLOWU
-#define DD_SLOWU 1  // dd_run: the pairs' slow path behind a uniform branch, predicated
-#endif
 #ifndef DD_SK64
 #define DD_SK64 1u  // the 64-byte instance (config 5's 30-bit codes everywhere): every pair
 #endif
 
-// Decode symbols into a byte stream in LDS: both bytes of an entry are
-// written, the count advances by the entry's symbols.
-// k_decode_items sizes for piece bytes IP: the output region of a lane
-// (<= (8 IP + 29) / 5 symbols, one byte of slack, dword aligned), the staged
-// dwords of a wave, the staged 16-byte chunks per lane
-__host__ __device__ constexpr uint32_t di_rb(uint32_t ip) { return (((8u * ip + 29u) / 5u) + 2u + 3u) & ~3u; }
-// A round's items span at most `span` input bytes: 64 items of IP bytes, or
-// (budgeted rounds, BI > 0) as many of the next 64 items as fit BI bytes.
-// Their output regions (di_rb of each item's bytes, laid back to back) then
-// take at most 8 BI / 5 + 64 (29 / 5 + 5) bytes.
-__host__ __device__ constexpr uint32_t di_span(uint32_t ip, uint32_t bi) { return bi ? bi : WAVE * ip; }
-__host__ __device__ constexpr uint32_t di_obb(uint32_t ip, uint32_t bi) {
-  return bi ? ((8u * bi) / 5u + 692u + 15u) & ~15u : WAVE * di_rb(ip);
-}
-__host__ __device__ constexpr uint32_t di_ibw(uint32_t span) {
-  return (((span + DD_OV + 64u) / 4u + 8u) + 3u) & ~3u;  // whole 16-byte chunks
-}
-__host__ __device__ constexpr uint32_t di_pf(uint32_t span) {
-  return (span + DD_OV + 8u + 32u + 16u * WAVE - 1u) / (16u * WAVE);
-}
-template <uint32_t IP, int IW, int LB, uint32_t BI = 0>
+// A decoder instance of k_decode_items: IP piece bytes (a longer string is
+// cut into items of IP bytes), IW waves per workgroup, LB lookup bits, BI a
+// round's input-byte budget (0: none, a round is 64 items), SK the period in
+// pairs at which dd_run serves long codes, tasks of TK units of TS strings.
+// decode_batch_auto's two (see decode_items for the pick and its measurements):
+struct DecHeader {  // header strings: whole strings as items, budgeted rounds
+  static constexpr uint32_t IP = DD_IP64, BI = DD_BI64, SK = DD_SK64, TS = DD_TS64, TK = DD_TK64;
+  static constexpr int IW = DD_IW64, LB = DD_LB64;
+};
+struct DecLong {  // long values: 40-byte pieces, ranges balanced by weight
+  static constexpr uint32_t IP = DD_IP40, BI = DD_BI40, SK = DD_SK40, TS = DD_TS40, TK = DD_TK40;
+  static constexpr int IW = DD_IW40, LB = DD_LB40;
+};
+
+// The output region of an item of `bytes` input bytes (<= (8 bytes + 29) / 5
+// symbols, one byte of slack, dword aligned).
+__host__ __device__ constexpr uint32_t di_rb(uint32_t bytes) { return (((8u * bytes + 29u) / 5u) + 2u + 3u) & ~3u; }
+// What an instance C's parameters must satisfy, and the sizes that follow
+// from them.
+template <class C>
+struct DI {
+  static_assert(C::TS >= 1 && C::TS * C::TK <= TASK_STR, "a task's strings map to lanes");
+  static_assert(C::TK == 1u || (C::TS == 32u && DD_TAILU * C::IW <= 64),
+                "tail units: 32 strings, two per 64 lanes");
+  static_assert(C::BI == 0u || C::IP <= C::BI, "a budgeted round takes at least its first item");
+  // workgroup ranges balanced by weight (pieces shorter than 64 bytes: long
+  // values, whose tasks differ several-fold in work)
+  static constexpr bool BAL = C::IP < 64u;
+  // A round's items span at most SPAN input bytes: 64 items of IP bytes, or
+  // (budgeted rounds, BI > 0) as many of the next 64 items as fit BI bytes.
+  // Their output regions (di_rb of each item's bytes, laid back to back) then
+  // take at most OBB = 8 BI / 5 + 64 (29 / 5 + 5) bytes.
+  static constexpr uint32_t SPAN = C::BI ? C::BI : WAVE * C::IP;
+  static constexpr uint32_t RB = di_rb(C::IP);  // a lane's region (no budget)
+  static constexpr uint32_t OBB = C::BI ? ((8u * C::BI) / 5u + 692u + 15u) & ~15u : WAVE * RB;
+  // the staged dwords of a wave (whole 16-byte chunks), the staged 16-byte
+  // chunks per lane
+  static constexpr uint32_t IBW = (((SPAN + DD_OV + 64u) / 4u + 8u) + 3u) & ~3u;
+  static constexpr uint32_t PF = (SPAN + DD_OV + 8u + 32u + 16u * WAVE - 1u) / (16u * WAVE);
+};
+template <class C>
 struct DIShared {  // k_decode_items
-  DecT<LB> T;  // first: the lookup at LDS offset 0
-  alignas(16) uint32_t ib[IW][di_ibw(di_span(IP, BI))];
-  alignas(16) uint32_t ob[IW][(di_obb(IP, BI) / 4 + 1 + 3) & ~3u];
+  DecT<C::LB> T;  // first: the lookup at LDS offset 0
+  alignas(16) uint32_t ib[C::IW][DI<C>::IBW];
+  alignas(16) uint32_t ob[C::IW][(DI<C>::OBB / 4 + 1 + 3) & ~3u];
   uint32_t claimed, claimed1;     // tasks / tail units of the workgroup's range claimed so far
   uint32_t range[2];              // the workgroup's task range (wave 0's search)
   uint8_t tperm[64];              // claim order of the range's tail units (largest first)
@@ -1692,35 +1670,6 @@ struct LdsPtrSink {
 };
 typedef LdsPtrSink DISink;
 
-// The item decoder's 16-byte input loads (DD_NTL: nontemporal).  Round 5
-// made them nontemporal so that the cache kept the next step's raw input --
-// a benefit only of a bench that re-encodes the same batch every step.  On
-// the round-6 bench, which rotates three distinct batches, plain loads are
-// no slower (bench, 100 steps, three alternations: 1966.1 / 1965.3 / 1968.4
-// GB/s against 1958.2 / 1957.9 / 1952.7 nontemporal; with one batch 2029.0 /
-// 2019.1 / 2033.1 against 2019.2 / 2029.5 / 2029.0), and the 20-byte warm-up
-// overlaps of neighbouring rounds are served by the cache again instead of
-// HBM (profiles/r06/bench/ntl_*).  (Nontemporal output stores: 0.374 vs
-// 0.209 ms.)
-#ifndef DD_NTL
-#define DD_NTL 0
-#endif
-__device__ __forceinline__ uint4 dd_ld16(const uint4 *p) {
-#if DD_NTL
-  const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void dd_st16(uint4 *p, uint4 v) { *p = v; }
-
-// The window of 32 stream bits from bit q + 1 of the staged words (q = bp - 1).
-__device__ __forceinline__ uint32_t dd_win(const lds_u32 *ib, uint32_t q) {
-  const uint32_t p = q >> 5;
-  return __builtin_amdgcn_alignbit(ib[p], ib[p + 1], ~q);
-}
-
 // Input word k (big-endian) of a decode: the wave's staged LDS copy.
 struct LdsIn {
   const lds_u32 *ib;
@@ -1754,7 +1703,7 @@ struct DDRun {
 // pass the first boundary >= bstop (bp <= bstop - 13: the first symbol of a
 // 2-symbol entry is <= 9 bits); pairs run while both steps qualify.  A code
 // longer than the lookup (entry 0) stalls the lane for the rest of the pair,
-// then goes through slow_entry; one that would pass the string end is its
+// then goes through long_entry; one that would pass the string end is its
 // tail and leaves the fast loop.  The last bits go through checked steps,
 // which also settle the tail: the undecoded t < 30 bits.
 #define DD_ADV(U)                                                        \
@@ -1801,7 +1750,7 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   int32_t nG = ~(G2 - 1);  // bp <= G2  <=>  (int) nq >= ~(G2 - 1)
   // the window words in before the loop (else the loop head waits for every
   // LDS access in flight, the prefetch of N included, each pair)
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+  wait_lgkmcnt0();
   // a code longer than the lookup inside the pair loop: decode it, or leave
   // the pair loop at EOS (failed) or at the string's tail (the careful steps
   // find it again).  Predicated, with `failed` a VGPR flag: the nested
@@ -1813,21 +1762,6 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   // path's dependent reads once for several lanes' codes (config 3, k = 2:
   // 258.1 -> 253.0 us; the 64-byte instance, which serves config 5's 30-bit
   // codes everywhere, keeps k = 1)
-#define DD_SLOW()                                                        \
-  do {                                                                   \
-    const uint32_t rem_ = bend - (~nq + 1u);                             \
-    const uint32_t e_ = slow_entry(T, __builtin_amdgcn_alignbit(A, B, nq), rem_); \
-    const bool eos_ = e_ == 0xFFFFFFFFu;                                 \
-    const bool ok_ = !eos_ && E_L1(e_) <= rem_;                          \
-    failed |= eos_ ? 1u : 0u;                                            \
-    nG = ok_ ? nG : INT32_MAX;                                           \
-    const uint32_t ek_ = ok_ ? e_ : 0u;                                  \
-    sink.put(ek_ & E_OUT2, E_CNT8(ek_));                                 \
-    const uint32_t U_ = E_USED(ek_);                                     \
-    if (SYNC) ls = U_;                                                   \
-    DD_ADV(U_);                                                          \
-    if (nslow) ++*nslow;                                                 \
-  } while (0)
   // The fast pairs run at raised wave priority: the SIMD issues their
   // dependent chain's VALU before other waves' staging, scans and stores
   // (config 3 decode 294.1 vs 297.7 us, config 2 50.6 vs 52.2; priority 3,
@@ -1875,18 +1809,19 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
         ls = 0;
       }
       DD_ADV(U1 + U2);
-#if DD_SLOWU
       // (the slow path behind one uniform branch, predicated per lane: the
       // wave takes it whenever one of its lanes met a long code -- on config
       // 3's bytes nearly every serving pair -- and the exec-mask save and
-      // restore of a divergent branch cost every time.  Round 6: config 3
-      // decode 213.5 / 207.4 vs 216.3 / 210.3 us, configs 2 and 5 -0.7 /
-      // -0.3 %, outputs equal; profiles/r06/ab/ab_slow_uniform.log)
+      // restore of a divergent branch, which this replaced, cost every time.
+      // Round 6: config 3 decode 213.5 / 207.4 vs 216.3 / 210.3 us, configs
+      // 2 and 5 -0.7 / -0.3 %, outputs equal;
+      // profiles/r06/ab/ab_slow_uniform.log)
       {
+        // (an e1 of 0 stalls e2 too; direct: e1 = 0 was decoded or stopped)
         const bool need = slow && e2 == 0u && (!kDirect || e1 != 0u);
         if (__ballot(need)) {
           const uint32_t rem_ = bend - (~nq + 1u);
-          const uint32_t e_ = slow_entry(T, __builtin_amdgcn_alignbit(A, B, nq), rem_);
+          const uint32_t e_ = long_entry(T, __builtin_amdgcn_alignbit(A, B, nq), rem_);
           const bool eos_ = need && e_ == 0xFFFFFFFFu;
           const bool ok_ = need && e_ != 0xFFFFFFFFu && E_L1(e_) <= rem_;
           failed |= eos_ ? 1u : 0u;
@@ -1899,15 +1834,10 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
           if (nslow) *nslow += need ? 1u : 0u;
         }
       }
-#else
-      if (slow && e2 == 0u && (!kDirect || e1 != 0u))
-        DD_SLOW(); /* (an e1 of 0 stalls e2 too; direct: e1 = 0 was decoded or stopped) */
-#endif
     }
   };
   auto pairs = [&](auto dir) {
     constexpr bool kDirect = decltype(dir)::value;
-#if DD_DPAIR
     if constexpr (SLOWK == 2u && !kDirect) {
       // SLOWK 2 as two pairs per trip, the second one serving long codes:
       // the slow-code period is static (no counter parity in SALU) and the
@@ -1927,18 +1857,18 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
       while ((int32_t)nq >= nG) pair(dir, true);
       return;
     }
-#endif
+    // (any other period: a pair counter's parity, which the trips above
+    // replaced for SLOWK 2)
     while ((int32_t)nq >= nG) {
       ++it;
       pair(dir, SLOWK == 1u || (it & (SLOWK - 1u)) == 0u);
     }
   };
   __builtin_amdgcn_s_setprio(1);
-  if (SLOWK == 1u && DD_DIRECT_MODE != 0 && direct) pairs(std::true_type{});
+  if (SLOWK == 1u && direct) pairs(std::true_type{});
   else pairs(std::false_type{});
   __builtin_amdgcn_s_setprio(0);
   if (nslow) *nslow += nlong;
-#undef DD_SLOW
   bp = ~nq + 1u;
   if (SYNC && !failed && (int32_t)bp >= (int32_t)bstop) {
     // the last pair passed bstop: its codeword boundaries in order are the
@@ -1968,7 +1898,7 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
       if (done == 0u) {
         const uint32_t w = __builtin_amdgcn_alignbit(A, B, nq);
         uint32_t e = T.lut[w >> (32 - TT::BITS)];
-        if (e == 0u) e = slow_entry(T, w, 30u);
+        if (e == 0u) e = long_entry(T, w, 30u);
         const uint32_t L1 = E_L1(e), adv = bp + L1 >= bstop ? L1 : E_USED(e);
         const bool bad = e == 0xFFFFFFFFu || bp + adv > bend;
         failed |= bad ? 1u : 0u;
@@ -1990,13 +1920,13 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   // branch
   // (the loop-carried flags are VGPR words: as lane-mask bools every merge
   // of them costs SALU in each step)
-#if DD_FSTEP
   // fast single steps first, while one lookup stays inside the string (bp +
   // BITS <= bend) and a 2-symbol entry's second code starts before bstop
   // (its first is <= BITS - 5 bits: bp <= bstop - (BITS - 4)): no stop rules
   // to predicate, a lane leaves on its own (exec mask), a long code is left
   // to the careful steps.  The careful steps then only settle the item's
-  // last code or two.  (Round 6: config 3 decode 212.7 / 211.0 vs 214.3 /
+  // last code or two; without these steps they took every code from where
+  // the pairs stopped.  (Round 6: config 3 decode 212.7 / 211.0 vs 214.3 /
   // 212.4 us, config 2 42.3 / 42.5 vs 43.1 / 43.2, config 5 59.7 / 60.2 vs
   // 60.3 / 61.0 in two interleaved sets, outputs equal;
   // profiles/r06/ab/ab_fast_single_steps.log)
@@ -2012,7 +1942,6 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
     }
     bp = ~nq + 1u;
   }
-#endif
   uint32_t done = failed, at_end = 0u, tt = 0u, twin = 0u;
   while (__ballot(done == 0u)) {
     const uint32_t w = __builtin_amdgcn_alignbit(A, B, nq);
@@ -2021,7 +1950,7 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
     uint32_t e = T.lut[w >> (32 - TT::BITS)];
     const bool slow = e == 0u && !stop;
     if (__ballot(slow)) {
-      if (slow) e = slow_entry(T, w, rem);
+      if (slow) e = long_entry(T, w, rem);
     }
     const bool eos = e == 0xFFFFFFFFu && !stop;  // EOS: the sticky failure state
     const uint32_t L1 = E_L1(e), U = E_USED(e);
@@ -2081,6 +2010,14 @@ __device__ __forceinline__ void dd_finish(const TT &T, bool failed, uint32_t t,
 // (status), a plain scan of the lanes' byte counts places the regions back
 // to back from the task's base, and each lane stores its bytes.
 // ---------------------------------------------------------------------------
+// The first of a range's tail units: [u_lo, u_hi) in units is whole tasks of
+// TK units up to it, then at most DD_TAILU x IW + TK - 1 single units.
+template <class C>
+__device__ __forceinline__ uint32_t di_tail_start(uint32_t u_lo, uint32_t u_hi) {
+  return max(u_lo, u_hi > u_lo + DD_TAILU * C::IW
+                       ? u_lo + ((u_hi - u_lo - DD_TAILU * C::IW) / C::TK) * C::TK
+                       : u_lo);
+}
 // The claim order of a workgroup range's tail units (k_decode_items, TK > 1):
 // largest first by items (ceil(E / IP) per string), so that the units claimed
 // last, whose end is the workgroup's, are the short ones.  Wave 0, after the
@@ -2088,15 +2025,13 @@ __device__ __forceinline__ void dd_finish(const TT &T, bool failed, uint32_t t,
 // waited ~5.5 us for it): the range's last DD_TAILU x IW units (<= 64, <= 64
 // x TS strings) are read as offsets, their items summed per unit, ranked.
 // (r_lo / r_hi in ranges of TK units, as the search returns them.)
-template <uint32_t IP, uint32_t TS, uint32_t TK, int IW>
+template <class C>
 __device__ __forceinline__ void dd_tail_order(const uint32_t *__restrict__ off, uint32_t n,
                                               uint32_t ntask, uint32_t r_lo, uint32_t r_hi,
                                               uint8_t *tperm, uint32_t lane) {
-  static_assert(TS == 32u && DD_TAILU * IW <= 64, "tail units: 32 strings, two per 64 lanes");
+  constexpr uint32_t IP = C::IP, TS = C::TS, TK = C::TK;
   const uint32_t u_lo = min(r_lo * TK, ntask), u_hi = min(r_hi * TK, ntask);
-  const uint32_t t_mid = max(u_lo, u_hi > u_lo + DD_TAILU * IW
-                                       ? u_lo + ((u_hi - u_lo - DD_TAILU * IW) / TK) * TK
-                                       : u_lo);
+  const uint32_t t_mid = di_tail_start<C>(u_lo, u_hi);
   const uint32_t nt = u_hi - t_mid;  // <= DD_TAILU * IW + TK - 1
   if (nt == 0u) return;
   const uint32_t s0 = t_mid * TS, s1 = min(u_hi * TS, n);
@@ -2121,18 +2056,26 @@ __device__ __forceinline__ void dd_tail_order(const uint32_t *__restrict__ off, 
   if (lane < nt) tperm[rank] = (uint8_t)lane;
 }
 
-template <uint32_t IP, int IW, int LB, uint32_t BI = 0, uint32_t SK = 1, uint32_t TS = TASK_STR,
-          uint32_t TK = 1>
-__global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__restrict__ src,
-                                                        const uint32_t *__restrict__ off,
-                                                        uint32_t n, uint8_t *__restrict__ dst,
-                                                        uint64_t dst_cap,
-                                                        uint32_t *__restrict__ dst_off,
-                                                        int32_t *__restrict__ status,
-                                                        uint16_t *__restrict__ fstate_out,
-                                                        uint8_t *__restrict__ flags_out) {
-  __shared__ DIShared<IP, IW, LB, BI> S;
-  constexpr uint32_t kSpan = di_span(IP, BI), kPF = di_pf(kSpan);
+// (One body.  Cut into phase functions over explicit state -- range, claim,
+// task header, item map, stage and prefetch, decode and verify, count,
+// placement, store, carry -- the same operations in the same order compile
+// to other register counts (long instance 86 -> 88 VGPRs) and, with the
+// prefetch loads indexed g[lane + 64 u] instead of *(g + lane + 64 u), 2.5 %
+// slower: tools/diag/patches/r7_decode_phases.patch,
+// profiles/r07/ab/ab_decode_phases.log.)
+template <class C>
+__global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__restrict__ src,
+                                                           const uint32_t *__restrict__ off,
+                                                           uint32_t n, uint8_t *__restrict__ dst,
+                                                           uint64_t dst_cap,
+                                                           uint32_t *__restrict__ dst_off,
+                                                           int32_t *__restrict__ status,
+                                                           uint16_t *__restrict__ fstate_out,
+                                                           uint8_t *__restrict__ flags_out) {
+  constexpr uint32_t IP = C::IP, BI = C::BI, SK = C::SK, TS = C::TS, TK = C::TK;
+  constexpr int IW = C::IW;
+  __shared__ DIShared<C> S;
+  constexpr uint32_t kSpan = DI<C>::SPAN, kPF = DI<C>::PF;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   lds_u32 *ibw = (lds_u32 *)S.ib[wv];
   const lds_u32 *ibe = ibw;
@@ -2154,7 +2097,7 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
   // (encoded bytes + DD_TASK_W per string) over the grid, its waves striding
   // over it (config 3: 348 vs 356 us); else the grid strides over all tasks
   // (the search costs a short batch more than it saves)
-  constexpr bool kBal = IP < 64u;
+  constexpr bool kBal = DI<C>::BAL;
   uint32_t t_lo, t_hi;
   {
     const uint32_t nwg = gridDim.x, g = blockIdx.x;
@@ -2207,7 +2150,7 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
       // decoding); a tail claim waits for it (in practice it is long ready)
       if constexpr (TK > 1u) {
         if (wv == 0) {
-          dd_tail_order<IP, TS, TK, IW>(off, n, ntask, t_lo, t_hi, S.tperm, lane);
+          dd_tail_order<C>(off, n, ntask, t_lo, t_hi, S.tperm, lane);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
           if (lane == 0) __hip_atomic_store((uint32_t *)&S.tready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -2233,10 +2176,12 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
                                                   : t_lo)
                                  : t_hi;
   uint32_t next_k = 0;
-  // (defer, DD_JIT_TAIL: a claim that finds the range's whole tasks gone
-  // returns kDefer and the wave claims its tail unit when its task ends:
-  // claimed one task ahead, the tail units were all handed out a task before
-  // the workgroup's end, by stale order, and its waves ended ~22 us apart)
+  // (defer: a claim that finds the range's whole tasks gone returns kDefer
+  // and the wave claims its tail unit when its task ends.  Claimed one task
+  // ahead, which this replaced, the tail units were all handed out a task
+  // before the workgroup's end, by stale order, and its waves ended ~22 us
+  // apart; round 5: config 3 decode 224.0 vs 231.1 and 215.9 vs 225.5 us,
+  // config 2 flat; profiles/r05/ab/ab_jit_tail.log)
   constexpr uint32_t kDefer = 0xFFFFFFFFu;
   auto claim_next = [&](bool defer, bool tail_only = false) -> uint32_t {
     uint32_t t = 0;
@@ -2261,7 +2206,7 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
     next_k = t < t_hi ? (t < t_mid ? TK : 1u) : 0u;
     return t;
   };
-  constexpr bool kJit = TK > 1u && DD_JIT_TAIL != 0;
+  constexpr bool kJit = TK > 1u;
   // a task's string offsets are loaded one task ahead, and the first round
   // of the next task is staged into registers during the current task's
   // last round (pf), so neither waits at a task start
@@ -2289,7 +2234,8 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
   // direct long codes (the 64-byte instance, see dd_run): on for the wave's
   // next round when DD_DIRECT_MIN of this round's lanes met a code past the
   // lookup (slow-path runs, or direct decodes of such codes; DD_DIRECT_KEEP
-  // of them to stay on)
+  // of them to stay on).  (Never direct, always direct and a ballot per pair
+  // all lost to this: the round-5 figures in dd_run's note.)
   bool dmode = false;
   uint32_t nslow = 0;
   for (uint32_t task = t_first; task < t_hi;) {
@@ -2356,14 +2302,14 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
       if (BI) {
         // budgeted round: the items of the next 64 that fit BI input bytes
         // (the first always does: IP <= BI), each lane's output region right
-        // after the one before (no region crosses the round's di_obb bytes)
+        // after the one before (no region crosses the round's OBB bytes)
         const uint32_t x = lane < nv ? e - s : 0u;
         const uint32_t cx = wave_incl_scan(x);
         nv = (uint32_t)__builtin_popcountll(__ballot(lane < nv && cx <= BI));
         const uint32_t rb = lane < nv ? di_rb(x) : 0u;
         my_ob = (lds_u8 *)S.ob[wv] + (wave_incl_scan(rb) - rb);
         my_rb = rb;
-        HD_CHECK(wave_incl_scan(rb) <= di_obb(IP, BI), 0x206u);
+        HD_CHECK(wave_incl_scan(rb) <= DI<C>::OBB, 0x206u);
         my_ob32 = (const lds_u32 *)my_ob;
       }
       const bool valid = lane < nv;
@@ -2373,14 +2319,14 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
       uint32_t IB, nchunk;
       round_range(R0, A, Z, IB, nchunk);
       const uint32_t IBX = IB - 16u;
-      const LdsIn inp{ibe HD_LIM(di_ibw(kSpan))};
+      const LdsIn inp{ibe HD_LIM(DI<C>::IBW)};
       // the prefetched chunks (pf) into the staging buffer, byte-swapped
       auto stage_pf = [&](uint32_t nch) {
 #pragma unroll
         for (uint32_t u = 0; u < kPF; ++u) {
           const uint32_t c = lane + WAVE * u;
           if (c < nch) {
-            HD_CHECK(4u * c + 8u <= di_ibw(kSpan), 0x201u);
+            HD_CHECK(4u * c + 8u <= DI<C>::IBW, 0x201u);
             u32x4 v;
             v.x = __builtin_bswap32(pf[u].x);
             v.y = __builtin_bswap32(pf[u].y);
@@ -2389,16 +2335,24 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
             *(lds_u32x4 *)(ibw + 4u * c + 4u) = v;
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
       };
       {
+        // (The 16-byte input loads are plain.  Round 5 made them nontemporal
+        // so that the cache kept the next step's raw input -- a benefit only
+        // of a bench that re-encodes the same batch every step.  On the
+        // round-6 bench, which rotates three distinct batches, plain loads
+        // are no slower (bench, 100 steps, three alternations: 1966.1 /
+        // 1965.3 / 1968.4 GB/s against 1958.2 / 1957.9 / 1952.7 nontemporal;
+        // with one batch 2029.0 / 2019.1 / 2033.1 against 2019.2 / 2029.5 /
+        // 2029.0), and the 20-byte warm-up overlaps of neighbouring rounds are
+        // served by the cache again instead of HBM (profiles/r06/bench/ntl_*).
+        // Nontemporal output stores: 0.374 vs 0.209 ms.)
         const uint4 *g = reinterpret_cast<const uint4 *>(src + IB);
         if (pf_IB != IB) {  // (not prefetched)
 #pragma unroll
           for (uint32_t u = 0; u < kPF; ++u)
-            if (lane + WAVE * u < nchunk) pf[u] = dd_ld16(g + lane + WAVE * u);
+            if (lane + WAVE * u < nchunk) pf[u] = *(g + lane + WAVE * u);
         }
         stage_pf(nchunk);
         // prefetch the next round: of this task, else the next task's first
@@ -2418,7 +2372,7 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
           const uint4 *gn = reinterpret_cast<const uint4 *>(src + IBn);
 #pragma unroll
           for (uint32_t u = 0; u < kPF; ++u)
-            if (lane + WAVE * u < ncn) pf[u] = dd_ld16(gn + lane + WAVE * u);
+            if (lane + WAVE * u < ncn) pf[u] = *(gn + lane + WAVE * u);
         }
       }
       if (carry_exit < DD_NONE) carry_exit -= 8u * (IB - IB_prev);
@@ -2493,7 +2447,7 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
           my_entry = pred;
         }
       }
-      if (SK == 1u && DD_DIRECT_MODE != 0) {
+      if (SK == 1u) {
         dmode = __builtin_popcountll(__ballot(nslow != 0u)) >=
                 (dmode ? DD_DIRECT_KEEP : DD_DIRECT_MIN);
         nslow = 0;
@@ -2570,18 +2524,14 @@ __global__ __launch_bounds__(WAVE * IW) void k_decode_items(const uint8_t *__res
       R0 = __builtin_amdgcn_readlane(e, nv - 1u);
       carry_exit = __builtin_amdgcn_readlane(last ? DD_NONE : my_exit, nv - 1u);
       carry_cnt = __builtin_amdgcn_readlane(seg, nv - 1u);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
     // ---- epilogue: output starts
     if (sl) {
       dst_off[t0 + lane] = (uint32_t)min(tbase + ost_me, dst_cap);
       if (t0 + lane == n - 1u) dst_off[n] = (uint32_t)min(tbase + run, dst_cap);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (kJit && next_task == kDefer) {
       next_task = claim_next(false, true);
       load_offs(next_task < t_hi ? next_task : ntask, next_k, na_l, nb_l);
@@ -2705,16 +2655,14 @@ static int hip_rv(hipError_t e) {
 }
 
 #ifndef HD_PART_ENC
-template <uint32_t IP, int IW, int LB, uint32_t BI = 0, uint32_t SK = 1, uint32_t TS = TASK_STR,
-          uint32_t TK = 1>
+template <class C>
 static void launch_decode_items(const uint8_t *src, const uint32_t *src_off, uint32_t n,
                                 uint8_t *dst, size_t dst_cap, uint32_t *dst_off,
                                 int32_t *status, uint16_t *fstate, uint8_t *flags,
                                 hipStream_t st) {
-  static_assert(TS >= 1 && TS * TK <= TASK_STR, "a task's strings map to lanes");
-  hipLaunchKernelGGL((k_decode_items<IP, IW, LB, BI, SK, TS, TK>),
-                     dim3(persistent_grid<k_decode_items<IP, IW, LB, BI, SK, TS, TK>, WAVE * IW, TS * TK * IW>(n)),
-                     dim3(WAVE * IW), 0, st, src, src_off, n, dst, (uint64_t)dst_cap, dst_off,
+  hipLaunchKernelGGL(k_decode_items<C>,
+                     dim3(persistent_grid<k_decode_items<C>, WAVE * C::IW, C::TS * C::TK * C::IW>(n)),
+                     dim3(WAVE * C::IW), 0, st, src, src_off, n, dst, (uint64_t)dst_cap, dst_off,
                      status, fstate, flags);
 }
 
@@ -2742,9 +2690,9 @@ static int decode_items(const uint8_t *src, const uint32_t *src_off, uint32_t n,
   if ((fstate == nullptr) != (flags == nullptr)) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   if ((uint64_t)dst_cap > 0xFFFFFFFFull) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;  // uint32 offsets
   if (enc_bytes <= 48ull * n)
-    launch_decode_items<DD_IP64, DD_IW64, DD_LB64, DD_BI64, DD_SK64, DD_TS64, DD_TK64>(src, src_off, n, dst, dst_cap, dst_off, status, fstate, flags, st);
+    launch_decode_items<DecHeader>(src, src_off, n, dst, dst_cap, dst_off, status, fstate, flags, st);
   else
-    launch_decode_items<DD_IP40, DD_IW40, DD_LB40, DD_BI40, DD_SK40, DD_TS40, DD_TK40>(src, src_off, n, dst, dst_cap, dst_off, status, fstate, flags, st);
+    launch_decode_items<DecLong>(src, src_off, n, dst, dst_cap, dst_off, status, fstate, flags, st);
   return hip_rv(hipGetLastError());
 }
 

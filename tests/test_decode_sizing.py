@@ -1,5 +1,5 @@
 """Host-side checks of the item decoder's LDS sizing (csrc/hd_huff.hip,
-di_rb / di_obb / di_ibw / di_span, restated here): a round's output regions
+di_rb and struct DI's OBB / IBW / SPAN, restated here): a round's output regions
 never pass the output buffer, and its staged input never passes the staging
 buffer, for plain rounds (64 items of at most P bytes) and budgeted rounds
 (as many of the next 64 items as fit BI bytes).  The kernel relies on these
