@@ -21,7 +21,9 @@
  *
  * Pool requirements (device API): pool base pointers 16-byte aligned; the
  * source pool readable up to align_up(off[N], 16) + 16 bytes (kernels load
- * aligned 16-byte words and unaligned 4-byte windows).  Offsets are uint32, so one batch's pool is
+ * aligned 16-byte words and unaligned 4-byte windows).  src_off[0] may be
+ * any value; only the source bytes from `src_off[0] & ~15` on are read.
+ * Offsets are uint32, so one batch's pool is
  * < 4 GiB; shard larger sets (multi-GPU).
  *
  * Error convention: 0 on success or a negative nghttp2_error code

@@ -5,8 +5,9 @@ checked against its buffer (csrc/hd_huff.hip HD_CHECK sites).
 A child process loads that build through NGHTTP2_AMD_LIB, runs the parity
 cases of tests/test_parity_gpu.py through it -- encode, both decode_batch_auto
 instances, the slot decoder, emit_strings, adversarial and window-edge
-inputs, NGHTTP2_HD_MAX_NV-sized and empty strings, one-tile batches -- and
-after each asks nghttp2_amd_hd__bounds_check for the first recorded
+inputs, NGHTTP2_HD_MAX_NV-sized and empty strings, one-tile batches, and the
+boundary grids of tests/boundary_batches.py (straddle, ends, tasks,
+round_words, long_pairs) -- and after each asks nghttp2_amd_hd__bounds_check for the first recorded
 violation, which must be none.  The report path itself is checked by the
 build's self-test kernel (site 0x1FF)."""
 import ctypes
@@ -27,6 +28,7 @@ import torch
 import nghttp2_amd
 from nghttp2_amd import workloads as W
 from oracle import oracle as O
+from tests import boundary_batches as BB
 from tests import test_parity_gpu as T
 
 L = nghttp2_amd.lib()
@@ -83,6 +85,19 @@ for tag, (enc, eoff) in (("adversarial", (pool, off)), ("window edges", (enc_w, 
     T.check_decode(codec, dev, enc, eoff, tag)
     for pick in ("items64", "pieces40"):
         T.auto_decode_check(codec, dev, enc, eoff, tag + " " + pick, pick=pick)
+    done(tag)
+# the boundary grids (tests/boundary_batches.py): the same calls
+for tag, (enc, eoff) in (("straddle", BB.straddle()), ("ends", BB.ends()), ("tasks", BB.tasks())):
+    T.check_decode(codec, dev, enc, eoff, tag)
+    for pick in ("items64", "pieces40"):
+        T.auto_decode_check(codec, dev, enc, eoff, tag + " " + pick, pick=pick)
+    done(tag)
+for tag, (pool, off) in (("round_words", BB.round_words()), ("long_pairs", BB.long_pairs())):
+    T.check_roundtrip(codec, dev, pool, off, tag)
+    enc, eoff = O.encode_batch(pool, off)
+    for pick in ("items64", "pieces40"):
+        T.auto_decode_check(codec, dev, enc, eoff, tag + " " + pick, pick=pick)
+    T.check_emit(codec, dev, pool, off, tag)
     done(tag)
 print("BOUNDS-OK")
 """ % REPO
