@@ -19,7 +19,6 @@
 // emit_table_size (:975-1128), add_hd_table_incremental (:1130-1195).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -34,40 +33,28 @@
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "../../include/nghttp2_amd_hd_testing.h"
+#include "hd_host.h"
 #include "host_threads.h"
-#include "hd_tokens.h"
 
 namespace {
 
-const uint32_t kEntryOverhead = 32;
-const uint32_t kStaticLen = 61;
-const char *const kStatic[kStaticLen][2] = {
-    {":authority", ""}, {":method", "GET"}, {":method", "POST"}, {":path", "/"},
-    {":path", "/index.html"}, {":scheme", "http"}, {":scheme", "https"}, {":status", "200"},
-    {":status", "204"}, {":status", "206"}, {":status", "304"}, {":status", "400"},
-    {":status", "404"}, {":status", "500"}, {"accept-charset", ""},
-    {"accept-encoding", "gzip, deflate"}, {"accept-language", ""}, {"accept-ranges", ""},
-    {"accept", ""}, {"access-control-allow-origin", ""}, {"age", ""}, {"allow", ""},
-    {"authorization", ""}, {"cache-control", ""}, {"content-disposition", ""},
-    {"content-encoding", ""}, {"content-language", ""}, {"content-length", ""},
-    {"content-location", ""}, {"content-range", ""}, {"content-type", ""}, {"cookie", ""},
-    {"date", ""}, {"etag", ""}, {"expect", ""}, {"expires", ""}, {"from", ""}, {"host", ""},
-    {"if-match", ""}, {"if-modified-since", ""}, {"if-none-match", ""}, {"if-range", ""},
-    {"if-unmodified-since", ""}, {"last-modified", ""}, {"link", ""}, {"location", ""},
-    {"max-forwards", ""}, {"proxy-authenticate", ""}, {"proxy-authorization", ""},
-    {"range", ""}, {"referer", ""}, {"refresh", ""}, {"retry-after", ""}, {"server", ""},
-    {"set-cookie", ""}, {"strict-transport-security", ""}, {"transfer-encoding", ""},
-    {"user-agent", ""}, {"vary", ""}, {"via", ""}, {"www-authenticate", ""}};
+using namespace hdhost;  // the static table, hip_ok, DevBuf / PinnedBuf
+const char *const kLayer = "deflate";  // (in hip_ok's messages)
 
 enum Mode { WITH_INDEXING, WITHOUT_INDEXING, NEVER_INDEXING };  // nghttp2_hd.h
 
-bool name_is(const uint8_t *name, size_t len, const char *s) {
-  return strlen(s) == len && memcmp(s, name, len) == 0;
+// the name (which = 0) or value (1) of static entry s is these bytes
+bool static_is(uint32_t s, int which, const uint8_t *p, size_t len) {
+  return kStaticLens.len[s][which] == len && memcmp(kStatic[s][which], p, len) == 0;
 }
 
 // lookup_token (lib/nghttp2_hd.c:137) and name_hash (:536-547): one FNV-1a
 // pass and a hashed probe (hd_tokens.h), shared with the GPU kernel.
 using hdtok::name_hash;
+// the NGHTTP2_TOKEN_* values (lib/nghttp2_hd.h:57-108) the indexing decision names
+constexpr int32_t kTokenPath = 3, kTokenAge = 20, kTokenAuthorization = 22, kTokenContentLength = 27,
+                  kTokenCookie = 31, kTokenEtag = 33, kTokenIfModifiedSince = 39, kTokenIfNoneMatch = 40,
+                  kTokenLocation = 45, kTokenSetCookie = 54;
 constexpr int32_t kLastStaticToken = 60;  // NGHTTP2_TOKEN_WWW_AUTHENTICATE
 
 struct Entry {
@@ -129,14 +116,10 @@ namespace {
 
 struct Engine {
   std::mutex mu;
-  uint8_t *h_in = nullptr, *h_out = nullptr;
-  uint32_t *h_off = nullptr;
-  size_t hin_cap = 0, hout_cap = 0, hoff_cap = 0;
-  uint8_t *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr;
-  uint32_t *d_off = nullptr;
-  size_t din_cap = 0, dout_cap = 0, dws_cap = 0, doff_cap = 0;
-  uint32_t *h_nt = nullptr, *d_nt = nullptr;  // name tokens and hashes
-  size_t hnt_cap = 0, dnt_cap = 0;
+  PinnedBuf h_in, h_out, h_off;  // strings in, framed literals out, uint32 offsets of both
+  DevBuf d_in, d_out, d_off, d_ws;
+  PinnedBuf h_nt;  // name hashes, then tokens
+  DevBuf d_nt;
 };
 // Batches of at least this many field names take their tokens and hashes
 // from one k_name_tokens launch (NGHTTP2_AMD_GPU_NAMES_MIN; 0 = always);
@@ -145,15 +128,9 @@ std::atomic<uint32_t> g_names_min{[] {
   const char *e = getenv("NGHTTP2_AMD_GPU_NAMES_MIN");
   return e ? (uint32_t)strtoul(e, nullptr, 10) : 2048u;
 }()};
-uint32_t gpu_names_min() { return g_names_min.load(); }
 Engine &engine() {
   static Engine e;
   return e;
-}
-bool hip_ok(hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  fprintf(stderr, "nghttp2_amd_hd (deflate): %s: %s\n", what, hipGetErrorString(e));
-  return false;
 }
 // Fault injection for the error paths (tests only, like the reference's
 // failmalloc suite, tests/failmalloc_test.c): the next n GPU stages of
@@ -165,24 +142,6 @@ bool fault_inject_gpu() {
     if (g_fail_gpu.compare_exchange_weak(k, k - 1)) return true;
   return false;
 }
-bool grow_host(void **p, size_t *cap, size_t need) {
-  if (need <= *cap) return true;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (!hip_ok(hipHostMalloc(p, need, hipHostMallocDefault), "hipHostMalloc")) return false;
-  *cap = need;
-  return true;
-}
-bool grow_dev(void **p, size_t *cap, size_t need) {
-  if (need <= *cap) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (!hip_ok(hipMalloc(p, need), "hipMalloc")) return false;
-  *cap = need;
-  return true;
-}
 
 // One piece of a block's wire: representation bytes, then up to two
 // literals (indices into the batch's literal list, -1 = none).
@@ -190,6 +149,309 @@ struct Piece {
   std::string bytes;
   int32_t lit[2] = {-1, -1};
 };
+using Lits = std::vector<std::pair<const uint8_t *, uint32_t>>;  // a block's literals: bytes, length
+
+// Pass 1's result: per block its pieces and the literals to frame; block i's
+// literals are the batch's litbase[i] + j, their bytes from rawbase[i] in the pool.
+struct Batch {
+  std::vector<std::vector<Piece>> pieces;
+  std::vector<Lits> lits;
+  std::vector<uint32_t> litbase;
+  std::vector<uint64_t> rawbase;
+};
+// The framed literals (pass 2's input): literal g is bytes[off[g] .. off[g + 1]).
+struct Framed {
+  const uint8_t *bytes = nullptr;
+  const uint32_t *off = nullptr;
+};
+
+// ---- the phases of nghttp2_amd_hd_deflate_blocks, each named after the trace mark that closes it
+using nghttp2_amd_host::parallel_for;
+
+// "names": the token and hash of every field name of the batch (lookup_token,
+// name_hash; deflate_nv, lib/nghttp2_hd.c:1388-1393) from one GPU launch over
+// the batch's names, before any deflater changes (a failure here leaves them
+// as they were).  fnt: hash[nf], then token[nf].  Holds the engine's lock.
+int stage_name_tokens(const nghttp2_amd_nv *names, uint32_t nf, void *stream, std::vector<uint32_t> *fnt) {
+  std::vector<uint64_t> nbase(nf + 1, 0);
+  for (uint32_t k = 0; k < nf; ++k) nbase[k + 1] = nbase[k] + names[k].namelen;
+  const uint64_t nraw = nbase[nf];
+  if (nraw > UINT32_MAX) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  const size_t in_bytes = ((size_t)nraw + 15u) / 16u * 16u + 16u;
+  const size_t off_bytes = ((size_t)nf + 1u) * sizeof(uint32_t), nt_bytes = 2u * (size_t)nf * sizeof(uint32_t);
+  std::lock_guard<std::mutex> guard(engine().mu);
+  Engine &E = engine();
+  hipStream_t st = (hipStream_t)stream;
+  if (!E.h_in.reserve(in_bytes, kLayer, false) || !E.h_off.reserve(off_bytes, kLayer, false) ||
+      !E.h_nt.reserve(nt_bytes, kLayer, false) || !E.d_in.reserve(in_bytes, kLayer) ||
+      !E.d_off.reserve(off_bytes, kLayer) || !E.d_nt.reserve(nt_bytes, kLayer))
+    return NGHTTP2_AMD_ERR_NOMEM;
+  uint8_t *const h_in = E.h_in.as<uint8_t>();
+  uint32_t *const h_off = E.h_off.as<uint32_t>(), *const h_nt = E.h_nt.as<uint32_t>();
+  parallel_for(nf, 4096, [&](size_t k) {
+    h_off[k] = (uint32_t)nbase[k];
+    if (names[k].namelen) memcpy(h_in + nbase[k], names[k].name, names[k].namelen);
+  });
+  h_off[nf] = (uint32_t)nraw;
+  memset(h_in + nraw, 0, in_bytes - nraw);
+  if (fault_inject_gpu() ||
+      !hip_ok(hipMemcpyAsync(E.d_in.p, h_in, in_bytes, hipMemcpyHostToDevice, st), kLayer, "H2D") ||
+      !hip_ok(hipMemcpyAsync(E.d_off.p, h_off, off_bytes, hipMemcpyHostToDevice, st), kLayer, "H2D"))
+    return NGHTTP2_AMD_ERR_FATAL;
+  uint32_t *const d_nt = E.d_nt.as<uint32_t>();
+  const int rv = nghttp2_amd_hd_name_tokens_batch(E.d_in.as<uint8_t>(), E.d_off.as<uint32_t>(), nf,
+                                                  (int32_t *)(d_nt + nf), d_nt, stream);
+  if (rv) return rv;
+  if (!hip_ok(hipMemcpyAsync(h_nt, d_nt, nt_bytes, hipMemcpyDeviceToHost, st), kLayer, "D2H") ||
+      !hip_ok(hipStreamSynchronize(st), kLayer, "sync"))
+    return NGHTTP2_AMD_ERR_FATAL;
+  fnt->assign(h_nt, h_nt + 2u * (size_t)nf);
+  return 0;
+}
+
+// deflate_nv's indexing mode (lib/nghttp2_hd.c:1373-1400): never index
+// authorization, short cookies and fields flagged NO_INDEX; else
+// hd_deflate_decide_indexing (:1358-1371).
+Mode decide_indexing(int32_t token, const nghttp2_amd_nv &nv, size_t bufsize_max) {
+  if (token == kTokenAuthorization || (token == kTokenCookie && nv.valuelen < 20) || (nv.flags & 1u))
+    return NEVER_INDEXING;
+  if (token == kTokenPath || token == kTokenAge || token == kTokenContentLength || token == kTokenEtag ||
+      token == kTokenIfModifiedSince || token == kTokenIfNoneMatch || token == kTokenLocation ||
+      token == kTokenSetCookie || nv.namelen + nv.valuelen + kEntryOverhead > bufsize_max * 3 / 4)
+    return WITHOUT_INDEXING;
+  return WITH_INDEXING;
+}
+
+// search_hd_table (lib/nghttp2_hd.c:1225-1249): the dynamic table newest
+// first (an exact match, else the newest name match; name only when never
+// indexing); a static name without a dynamic exact match searches the static
+// table instead (search_static_table, :1201-1223).  The 0-based index of the
+// match, or -1; *exact: name and value both match.
+int64_t search_tables(const nghttp2_amd_hd_deflater *d, const nghttp2_amd_nv &nv, uint32_t nh, int32_t token,
+                      bool name_only, bool *exact) {
+  int64_t idx = -1;
+  *exact = false;
+  auto bucket = d->by_hash.find(nh);
+  if (bucket != d->by_hash.end()) {
+    const std::deque<uint64_t> &seqs = bucket->second;
+    for (size_t r = seqs.size(); r-- > 0;) {  // newest first
+      const size_t t = (size_t)(d->next_seq - 1u - seqs[r]);
+      const Entry &e = d->table[t];
+      if (e.name.size() != nv.namelen || memcmp(e.name.data(), nv.name, nv.namelen) != 0) continue;
+      if (idx < 0) {
+        idx = (int64_t)(kStaticLen + t);
+        if (name_only) break;
+      }
+      if (e.value.size() == nv.valuelen && memcmp(e.value.data(), nv.value, nv.valuelen) == 0) {
+        *exact = true;
+        return (int64_t)(kStaticLen + t);
+      }
+    }
+  }
+  if (token < 0 || token > kLastStaticToken) return idx;
+  if (!name_only)
+    for (uint32_t s = (uint32_t)token; s < kStaticLen && static_is(s, 0, nv.name, nv.namelen); ++s)
+      if (static_is(s, 1, nv.value, nv.valuelen)) {
+        *exact = true;
+        return s;
+      }
+  return token;
+}
+
+// deflate_nv (lib/nghttp2_hd.c:1373-1467) for one field with name hash nh and
+// token: its piece appended to P, its literals to L, the deflater's table
+// updated (add_hd_table_incremental).
+void deflate_nv(nghttp2_amd_hd_deflater *d, const nghttp2_amd_nv &nv, uint32_t nh, int32_t token,
+                std::vector<Piece> &P, Lits &L) {
+  auto lit = [&L](const uint8_t *p, size_t len) {
+    L.emplace_back(p, (uint32_t)len);
+    return (int32_t)L.size() - 1;
+  };
+  const Mode mode = decide_indexing(token, nv, d->bufsize_max);
+  bool exact;
+  const int64_t idx = search_tables(d, nv, nh, token, mode == NEVER_INDEXING, &exact);
+  Piece pc;
+  if (exact) {  // emit_indexed_block (:975-993)
+    put_int(pc.bytes, (uint32_t)idx + 1u, 7, 0x80);
+    P.push_back(pc);
+    return;
+  }
+  if (mode == WITH_INDEXING) d->add(nv.name, nv.namelen, nv.value, nv.valuelen, nh);
+  const uint8_t first = mode == WITH_INDEXING ? 0x40 : mode == WITHOUT_INDEXING ? 0x00 : 0x10;
+  if (idx < 0) {  // emit_newname_block (:1104-1128)
+    pc.bytes.push_back((char)first);
+    pc.lit[0] = lit(nv.name, nv.namelen);
+  } else {  // emit_indname_block (:1062-1102)
+    put_int(pc.bytes, (uint32_t)idx + 1u, mode == WITH_INDEXING ? 6 : 4, first);
+  }
+  pc.lit[1] = lit(nv.value, nv.valuelen);
+  P.push_back(pc);
+}
+
+// nghttp2_hd_deflate_hd_bufs (lib/nghttp2_hd.c:1469-1505) for block i, its
+// fields nva[0 .. n): the pending table size updates, then each field.  fnt:
+// the fields' hashes and tokens from stage_name_tokens (fnt[k] and
+// fnt[fnt_tok + k]), or null for the host lookup.
+int32_t deflate_block(nghttp2_amd_hd_deflater *d, const nghttp2_amd_nv *nva, uint32_t n, const uint32_t *fnt,
+                      uint32_t fnt_tok, std::vector<Piece> &P, Lits &L) {
+  if (d->bad) return NGHTTP2_AMD_ERR_HEADER_COMP;
+  if (d->notify) {  // :1477-1494
+    const size_t mn = d->min_max;
+    d->notify = false;
+    d->min_max = UINT32_MAX;
+    Piece pc;
+    if (d->bufsize_max > mn) put_int(pc.bytes, (uint32_t)mn, 5, 0x20);
+    put_int(pc.bytes, (uint32_t)d->bufsize_max, 5, 0x20);
+    P.push_back(pc);
+  }
+  for (uint32_t k = 0; k < n; ++k) {
+    const nghttp2_amd_nv &nv = nva[k];
+    const uint32_t nh = fnt ? fnt[k] : name_hash(nv.name, nv.namelen);
+    const int32_t token = fnt ? (int32_t)fnt[fnt_tok + k] : hdtok::lookup_token(nv.name, nv.namelen, nh);
+    deflate_nv(d, nv, nh, token, P, L);
+  }
+  return 0;
+}
+
+// "tables" -- pass 1: every block's representations against its deflater's
+// table; one task per connection, its lists in batch order (connections are
+// independent).  Then the batch's literal numbering.
+void deflate_tables(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks, const nghttp2_amd_nv *nva,
+                    const uint32_t *block_nv_off, const std::vector<uint32_t> &fnt, int32_t *block_status,
+                    Batch *B) {
+  B->pieces.resize(nblocks);
+  B->lits.resize(nblocks);
+  const uint32_t f0 = block_nv_off[0], nf = block_nv_off[nblocks] - f0;
+  // the batch's lists per connection, in batch order; the parallel region
+  // only reads `lists` (a vector indexed by connection number)
+  std::unordered_map<nghttp2_amd_hd_deflater *, uint32_t> conn_of;
+  std::vector<std::vector<uint32_t>> lists;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    auto it = conn_of.emplace(deflaters[i], (uint32_t)lists.size()).first;
+    if (it->second == lists.size()) lists.emplace_back();
+    lists[it->second].push_back(i);
+  }
+  parallel_for(lists.size(), 1, [&](size_t c) {
+    for (uint32_t i : lists[c]) {
+      const uint32_t a = block_nv_off[i];
+      block_status[i] = deflate_block(deflaters[i], nva + a, block_nv_off[i + 1] - a,
+                                      fnt.empty() ? nullptr : fnt.data() + (a - f0), nf, B->pieces[i], B->lits[i]);
+    }
+  });
+  B->litbase.assign(nblocks + 1, 0);
+  B->rawbase.assign(nblocks + 1, 0);
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    uint64_t r = 0;
+    for (auto &l : B->lits[i]) r += l.second;
+    B->litbase[i + 1] = B->litbase[i] + (uint32_t)B->lits[i].size();
+    B->rawbase[i + 1] = B->rawbase[i] + r;
+  }
+}
+
+// "gpu": every literal of the batch framed in one launch (emit_string): H2D
+// of the literal pool and its offsets, emit_strings, D2H of the framed
+// offsets and then of the framed bytes they total.  Called with the engine's
+// lock held; *fr points into the engine's pinned pools.
+int frame_literals(Engine &E, uint32_t nblocks, const Batch &B, void *stream, Framed *fr) {
+  const uint32_t nl = B.litbase[nblocks];
+  if (!nl) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t raw = B.rawbase[nblocks];
+  // uint32 offsets: the framed literals (raw + <= 6 prefix bytes each)
+  if (nghttp2_amd_hd_emit_strings_bound(raw, nl) > UINT32_MAX) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  const size_t in_bytes = ((size_t)raw + 15u) / 16u * 16u + 16u;
+  const size_t out_bytes = nghttp2_amd_hd_emit_strings_bound(raw, nl);
+  const size_t ws = nghttp2_amd_hd_emit_strings_workspace_size(raw, nl);
+  const size_t slots = (size_t)nl + 1u, off_bytes = 2u * slots * sizeof(uint32_t);  // raw, then framed
+  if (!E.h_in.reserve(in_bytes, kLayer, false) || !E.h_out.reserve(out_bytes, kLayer, false) ||
+      !E.h_off.reserve(off_bytes, kLayer, false) || !E.d_in.reserve(in_bytes, kLayer) ||
+      !E.d_out.reserve(out_bytes, kLayer) || !E.d_ws.reserve(ws, kLayer) || !E.d_off.reserve(off_bytes, kLayer))
+    return NGHTTP2_AMD_ERR_NOMEM;
+  uint8_t *const h_in = E.h_in.as<uint8_t>();
+  uint32_t *const h_off = E.h_off.as<uint32_t>(), *const d_off = E.d_off.as<uint32_t>();
+  // the literal pool and its offsets, block by block
+  parallel_for(nblocks, 256, [&](size_t i) {
+    uint32_t o = (uint32_t)B.rawbase[i];
+    uint32_t k = B.litbase[i];
+    for (auto &l : B.lits[i]) {
+      h_off[k++] = o;
+      if (l.second) memcpy(h_in + o, l.first, l.second);
+      o += l.second;
+    }
+  });
+  h_off[nl] = (uint32_t)raw;
+  memset(h_in + raw, 0, in_bytes - raw);
+  uint32_t *d_fo = d_off + slots, *h_fo = h_off + slots;
+  if (fault_inject_gpu() ||
+      !hip_ok(hipMemcpyAsync(E.d_in.p, h_in, in_bytes, hipMemcpyHostToDevice, st), kLayer, "H2D") ||
+      !hip_ok(hipMemcpyAsync(d_off, h_off, slots * sizeof(uint32_t), hipMemcpyHostToDevice, st), kLayer, "H2D"))
+    return NGHTTP2_AMD_ERR_FATAL;
+  const int rv = nghttp2_amd_hd_emit_strings_batch(E.d_in.as<uint8_t>(), d_off, nl, raw, E.d_out.as<uint8_t>(),
+                                                   out_bytes, d_fo, E.d_ws.p, ws, stream);
+  if (rv) return rv;
+  if (!hip_ok(hipMemcpyAsync(h_fo, d_fo, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st), kLayer, "D2H") ||
+      !hip_ok(hipStreamSynchronize(st), kLayer, "sync"))
+    return NGHTTP2_AMD_ERR_FATAL;
+  if (!hip_ok(hipMemcpyAsync(E.h_out.p, E.d_out.p, h_fo[nl], hipMemcpyDeviceToHost, st), kLayer, "D2H") ||
+      !hip_ok(hipStreamSynchronize(st), kLayer, "sync"))
+    return NGHTTP2_AMD_ERR_FATAL;
+  *fr = Framed{E.h_out.as<uint8_t>(), h_fo};
+  return 0;
+}
+
+// Block i's wire in order, as runs of bytes: f(ptr, len) for each piece's
+// representation bytes and then each of its framed literals.
+template <class F>
+void for_each_run(const Batch &B, size_t i, const Framed &fr, F &&f) {
+  for (const Piece &pc : B.pieces[i]) {
+    f((const uint8_t *)pc.bytes.data(), pc.bytes.size());
+    for (int j = 0; j < 2; ++j) {
+      if (pc.lit[j] < 0) continue;
+      const uint32_t g = B.litbase[i] + (uint32_t)pc.lit[j];
+      f(fr.bytes + fr.off[g], (size_t)(fr.off[g + 1] - fr.off[g]));
+    }
+  }
+}
+
+// "wire" -- pass 2: each block's wire size, placement in block order, then
+// the bytes.  Returns 0, or BUFFER_ERROR when a block did not fit.
+int place_wire(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks, const Batch &B, const Framed &fr,
+               uint8_t *out, size_t out_cap, uint32_t *out_off, int32_t *block_status) {
+  std::vector<size_t> need(nblocks, 0);
+  parallel_for(nblocks, 256, [&](size_t i) {
+    size_t n = 0;
+    for_each_run(B, i, fr, [&](const uint8_t *, size_t len) { n += len; });
+    need[i] = n;
+  });
+  size_t o = 0;
+  int ret = 0;
+  out_off[0] = 0;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    if (block_status[i] == 0 && deflaters[i]->bad) {
+      // an earlier block of this deflater ran out of room in this call:
+      // later ones fail as nghttp2_hd_deflate_hd_bufs does (:1475-1477)
+      block_status[i] = NGHTTP2_AMD_ERR_HEADER_COMP;
+    } else if (block_status[i] == 0 && (o + need[i] > out_cap || o + need[i] > UINT32_MAX)) {
+      // INSUFF_BUFSIZE in nghttp2_hd_deflate_hd2 (:1546-1547); the deflater turns bad
+      block_status[i] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+      deflaters[i]->bad = true;
+      ret = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+    } else if (block_status[i] == 0) {
+      block_status[i] = (int32_t)need[i];
+      o += need[i];
+    }
+    out_off[i + 1] = (uint32_t)o;
+  }
+  parallel_for(nblocks, 256, [&](size_t i) {
+    if (block_status[i] < 0) return;
+    uint8_t *w = out + out_off[i];
+    for_each_run(B, i, fr, [&](const uint8_t *p, size_t len) {
+      memcpy(w, p, len);
+      w += len;
+    });
+  });
+  return ret;
+}
 
 }  // namespace
 
@@ -240,10 +502,10 @@ int nghttp2_amd_hd_deflate_get_table_entry(nghttp2_amd_hd_deflater *d, size_t id
   if (!d || idx == 0 || idx > d->table.size() + kStaticLen) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   --idx;
   if (idx < kStaticLen) {
-    *name = (const uint8_t *)kStatic[idx][0];
-    *namelen = strlen(kStatic[idx][0]);
-    *value = (const uint8_t *)kStatic[idx][1];
-    *valuelen = strlen(kStatic[idx][1]);
+    const char *n, *v;
+    static_entry((uint32_t)idx, &n, namelen, &v, valuelen);
+    *name = (const uint8_t *)n;
+    *value = (const uint8_t *)v;
   } else {
     const Entry &e = d->table[idx - kStaticLen];
     *name = (const uint8_t *)e.name.data();
@@ -285,174 +547,16 @@ int nghttp2_amd_hd_deflate_blocks(nghttp2_amd_hd_deflater *const *deflaters, uin
   for (uint32_t i = 0; i < nblocks; ++i)
     if (!deflaters[i] || block_nv_off[i] > block_nv_off[i + 1]) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
 
-  using nghttp2_amd_host::parallel_for;
   nghttp2_amd_host::Pool::CallScope scope;  // workers spin between this call's phases only
   nghttp2_amd_host::Phases ph("deflate");
-  // ---- the token and hash of every field name of the batch (lookup_token,
-  // name_hash; deflate_nv, lib/nghttp2_hd.c:1388-1393): one GPU launch over
-  // the batch's names, before any deflater changes (a failure here leaves
-  // the deflaters as they were)
   const uint32_t f0 = block_nv_off[0], nf = block_nv_off[nblocks] - f0;
-  std::vector<uint32_t> fnt;  // hash[nf], then token[nf]
-  if (nf && nf >= gpu_names_min()) {
-    std::vector<uint64_t> nbase(nf + 1, 0);
-    for (uint32_t k = 0; k < nf; ++k) nbase[k + 1] = nbase[k] + nva[f0 + k].namelen;
-    const uint64_t nraw = nbase[nf];
-    if (nraw > UINT32_MAX) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-    const size_t in_bytes = ((size_t)nraw + 15u) / 16u * 16u + 16u;
-    std::lock_guard<std::mutex> guard(engine().mu);
-    Engine &E = engine();
-    hipStream_t st = (hipStream_t)stream;
-    if (!grow_host((void **)&E.h_in, &E.hin_cap, in_bytes) ||
-        !grow_host((void **)&E.h_off, &E.hoff_cap, ((size_t)nf + 1u) * sizeof(uint32_t)) ||
-        !grow_host((void **)&E.h_nt, &E.hnt_cap, 2u * (size_t)nf * sizeof(uint32_t)) ||
-        !grow_dev((void **)&E.d_in, &E.din_cap, in_bytes) ||
-        !grow_dev((void **)&E.d_off, &E.doff_cap, ((size_t)nf + 1u) * sizeof(uint32_t)) ||
-        !grow_dev((void **)&E.d_nt, &E.dnt_cap, 2u * (size_t)nf * sizeof(uint32_t)))
-      return NGHTTP2_AMD_ERR_NOMEM;
-    parallel_for(nf, 4096, [&](size_t k) {
-      E.h_off[k] = (uint32_t)nbase[k];
-      if (nva[f0 + k].namelen) memcpy(E.h_in + nbase[k], nva[f0 + k].name, nva[f0 + k].namelen);
-    });
-    E.h_off[nf] = (uint32_t)nraw;
-    memset(E.h_in + nraw, 0, in_bytes - nraw);
-    if (fault_inject_gpu() ||
-        !hip_ok(hipMemcpyAsync(E.d_in, E.h_in, in_bytes, hipMemcpyHostToDevice, st), "H2D") ||
-        !hip_ok(hipMemcpyAsync(E.d_off, E.h_off, ((size_t)nf + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D"))
-      return NGHTTP2_AMD_ERR_FATAL;
-    int rv = nghttp2_amd_hd_name_tokens_batch(E.d_in, E.d_off, nf, (int32_t *)(E.d_nt + nf), E.d_nt, stream);
-    if (rv) return rv;
-    if (!hip_ok(hipMemcpyAsync(E.h_nt, E.d_nt, 2u * (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H") ||
-        !hip_ok(hipStreamSynchronize(st), "sync"))
-      return NGHTTP2_AMD_ERR_FATAL;
-    fnt.assign(E.h_nt, E.h_nt + 2u * (size_t)nf);
+  std::vector<uint32_t> fnt;  // the names' hashes and tokens; empty: looked up on the host
+  if (nf && nf >= g_names_min.load()) {
+    if (const int rv = stage_name_tokens(nva + f0, nf, stream, &fnt)) return rv;
     ph.mark("names");
   }
-  // ---- pass 1: representations; one task per connection, its lists in
-  // batch order (connections are independent)
-  std::vector<std::vector<Piece>> pieces(nblocks);
-  std::vector<std::vector<std::pair<const uint8_t *, uint32_t>>> blits(nblocks);
-  auto deflate_list = [&](uint32_t i) {
-    std::vector<std::pair<const uint8_t *, uint32_t>> &L = blits[i];
-    auto lit = [&](const uint8_t *p, size_t len) {
-      L.emplace_back(p, (uint32_t)len);
-      return (int32_t)(L.size() - 1);
-    };
-      nghttp2_amd_hd_deflater *d = deflaters[i];
-    std::vector<Piece> &P = pieces[i];
-    if (d->bad) {
-      block_status[i] = NGHTTP2_AMD_ERR_HEADER_COMP;
-      return;
-    }
-    block_status[i] = 0;
-    if (d->notify) {  // nghttp2_hd_deflate_hd_bufs, lib/nghttp2_hd.c:1477-1494
-      const size_t mn = d->min_max;
-      d->notify = false;
-      d->min_max = UINT32_MAX;
-      Piece pc;
-      if (d->bufsize_max > mn) put_int(pc.bytes, (uint32_t)mn, 5, 0x20);
-      put_int(pc.bytes, (uint32_t)d->bufsize_max, 5, 0x20);
-      P.push_back(pc);
-    }
-    for (uint32_t k = block_nv_off[i]; k < block_nv_off[i + 1]; ++k) {
-      const nghttp2_amd_nv &nv = nva[k];
-      const uint32_t nh = fnt.empty() ? name_hash(nv.name, nv.namelen) : fnt[k - f0];
-      const int32_t token = fnt.empty() ? hdtok::lookup_token(nv.name, nv.namelen, nh)
-                                        : (int32_t)fnt[nf + (k - f0)];
-      const size_t room = nv.namelen + nv.valuelen + kEntryOverhead;
-      // deflate_nv (:1373-1400): never-index authorization, short cookies
-      // and fields flagged NO_INDEX; hd_deflate_decide_indexing (:1358-1371)
-      Mode mode;
-      if (token == 22 /* authorization */ || (token == 31 /* cookie */ && nv.valuelen < 20) ||
-          (nv.flags & 1u)) {
-        mode = NEVER_INDEXING;
-      } else if (token == 3 /* :path */ || token == 20 /* age */ || token == 27 /* content-length */ ||
-                 token == 33 /* etag */ || token == 39 /* if-modified-since */ ||
-                 token == 40 /* if-none-match */ || token == 45 /* location */ ||
-                 token == 54 /* set-cookie */ || room > d->bufsize_max * 3 / 4) {
-        mode = WITHOUT_INDEXING;
-      } else {
-        mode = WITH_INDEXING;
-      }
-      // search_hd_table (:1225-1249): the dynamic table newest first (an
-      // exact match, else the newest name match; name only when never
-      // indexing); a static name without a dynamic exact match searches the
-      // static table instead
-      const bool name_only = mode == NEVER_INDEXING;
-      int64_t idx = -1;
-      bool exact = false;
-      auto bucket = d->by_hash.find(nh);
-      if (bucket != d->by_hash.end()) {
-        const std::deque<uint64_t> &seqs = bucket->second;
-        for (size_t r = seqs.size(); r-- > 0;) {  // newest first
-          const size_t t = (size_t)(d->next_seq - 1u - seqs[r]);
-          const Entry &e = d->table[t];
-          if (e.name.size() != nv.namelen || memcmp(e.name.data(), nv.name, nv.namelen) != 0) continue;
-          if (idx < 0) {
-            idx = (int64_t)(kStaticLen + t);
-            if (name_only) break;
-          }
-          if (e.value.size() == nv.valuelen && memcmp(e.value.data(), nv.value, nv.valuelen) == 0) {
-            idx = (int64_t)(kStaticLen + t);
-            exact = true;
-            break;
-          }
-        }
-      }
-      if (!exact && token >= 0 && token <= kLastStaticToken) {  // search_static_table (:1201-1223)
-        idx = token;
-        if (!name_only) {
-          for (uint32_t s = (uint32_t)token; s < kStaticLen && name_is(nv.name, nv.namelen, kStatic[s][0]); ++s) {
-            if (strlen(kStatic[s][1]) == nv.valuelen && memcmp(kStatic[s][1], nv.value, nv.valuelen) == 0) {
-              idx = s;
-              exact = true;
-              break;
-            }
-          }
-        }
-      }
-      Piece pc;
-      if (exact) {  // emit_indexed_block (:975-993)
-        put_int(pc.bytes, (uint32_t)idx + 1u, 7, 0x80);
-        P.push_back(pc);
-        continue;
-      }
-      if (mode == WITH_INDEXING) d->add(nv.name, nv.namelen, nv.value, nv.valuelen, nh);
-      const uint8_t first = mode == WITH_INDEXING ? 0x40 : mode == WITHOUT_INDEXING ? 0x00 : 0x10;
-      if (idx < 0) {  // emit_newname_block (:1104-1128)
-        pc.bytes.push_back((char)first);
-        pc.lit[0] = lit(nv.name, nv.namelen);
-      } else {  // emit_indname_block (:1062-1102)
-        put_int(pc.bytes, (uint32_t)idx + 1u, mode == WITH_INDEXING ? 6 : 4, first);
-      }
-      pc.lit[1] = lit(nv.value, nv.valuelen);
-      P.push_back(pc);
-    }
-  };
-  {
-    // the batch's lists per connection, in batch order; the parallel region
-    // only reads `lists` (a vector indexed by connection number)
-    std::unordered_map<nghttp2_amd_hd_deflater *, uint32_t> conn_of;
-    std::vector<std::vector<uint32_t>> lists;
-    for (uint32_t i = 0; i < nblocks; ++i) {
-      auto it = conn_of.emplace(deflaters[i], (uint32_t)lists.size()).first;
-      if (it->second == lists.size()) lists.emplace_back();
-      lists[it->second].push_back(i);
-    }
-    parallel_for(lists.size(), 1, [&](size_t c) {
-      for (uint32_t i : lists[c]) deflate_list(i);
-    });
-  }
-  // literal numbering: block i's literals are litbase[i] + j
-  std::vector<uint32_t> litbase(nblocks + 1, 0);
-  std::vector<uint64_t> rawbase(nblocks + 1, 0);
-  for (uint32_t i = 0; i < nblocks; ++i) {
-    uint64_t r = 0;
-    for (auto &l : blits[i]) r += l.second;
-    litbase[i + 1] = litbase[i] + (uint32_t)blits[i].size();
-    rawbase[i + 1] = rawbase[i] + r;
-  }
-
+  Batch B;
+  deflate_tables(deflaters, nblocks, nva, block_nv_off, fnt, block_status, &B);
   ph.mark("tables");
   // Pass 1 has changed the deflaters (entries inserted, size updates
   // consumed).  From here on a failure leaves the encoder tables ahead of
@@ -469,110 +573,11 @@ int nghttp2_amd_hd_deflate_blocks(nghttp2_amd_hd_deflater *const *deflaters, uin
     out_off[0] = 0;
     return rv;
   };
-  // ---- GPU: frame every literal of the batch (emit_string)
-  const uint32_t nl = litbase[nblocks];
   std::lock_guard<std::mutex> guard(engine().mu);
-  Engine &E = engine();
-  const uint8_t *fr = nullptr;
-  const uint32_t *froff = nullptr;
-  if (nl) {
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t raw = rawbase[nblocks];
-    // uint32 offsets: the framed literals (raw + <= 6 prefix bytes each)
-    if (nghttp2_amd_hd_emit_strings_bound(raw, nl) > UINT32_MAX)
-      return fail_batch(NGHTTP2_AMD_ERR_INVALID_ARGUMENT);
-    const size_t in_bytes = ((size_t)raw + 15u) / 16u * 16u + 16u;
-    const size_t out_bytes = nghttp2_amd_hd_emit_strings_bound(raw, nl);
-    const size_t ws = nghttp2_amd_hd_emit_strings_workspace_size(raw, nl);
-    if (!grow_host((void **)&E.h_in, &E.hin_cap, in_bytes) ||
-        !grow_host((void **)&E.h_out, &E.hout_cap, out_bytes) ||
-        !grow_host((void **)&E.h_off, &E.hoff_cap, 2u * ((size_t)nl + 1u) * sizeof(uint32_t)) ||
-        !grow_dev((void **)&E.d_in, &E.din_cap, in_bytes) ||
-        !grow_dev((void **)&E.d_out, &E.dout_cap, out_bytes) ||
-        !grow_dev((void **)&E.d_ws, &E.dws_cap, ws) ||
-        !grow_dev((void **)&E.d_off, &E.doff_cap, 2u * ((size_t)nl + 1u) * sizeof(uint32_t)))
-      return fail_batch(NGHTTP2_AMD_ERR_NOMEM);
-    // the literal pool and its offsets, block by block
-    parallel_for(nblocks, 256, [&](size_t i) {
-      uint32_t o = (uint32_t)rawbase[i];
-      uint32_t k = litbase[i];
-      for (auto &l : blits[i]) {
-        E.h_off[k++] = o;
-        if (l.second) memcpy(E.h_in + o, l.first, l.second);
-        o += l.second;
-      }
-    });
-    E.h_off[nl] = (uint32_t)raw;
-    memset(E.h_in + raw, 0, in_bytes - raw);
-    uint32_t *d_fo = E.d_off + (nl + 1);
-    uint32_t *h_fo = E.h_off + (nl + 1);
-    if (fault_inject_gpu() ||
-        !hip_ok(hipMemcpyAsync(E.d_in, E.h_in, in_bytes, hipMemcpyHostToDevice, st), "H2D") ||
-        !hip_ok(hipMemcpyAsync(E.d_off, E.h_off, (nl + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D"))
-      return fail_batch(NGHTTP2_AMD_ERR_FATAL);
-    int rv = nghttp2_amd_hd_emit_strings_batch(E.d_in, E.d_off, nl, raw, E.d_out, out_bytes, d_fo,
-                                               E.d_ws, ws, stream);
-    if (rv) return fail_batch(rv);
-    if (!hip_ok(hipMemcpyAsync(h_fo, d_fo, (nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H") ||
-        !hip_ok(hipStreamSynchronize(st), "sync"))
-      return fail_batch(NGHTTP2_AMD_ERR_FATAL);
-    if (!hip_ok(hipMemcpyAsync(E.h_out, E.d_out, h_fo[nl], hipMemcpyDeviceToHost, st), "D2H") ||
-        !hip_ok(hipStreamSynchronize(st), "sync"))
-      return fail_batch(NGHTTP2_AMD_ERR_FATAL);
-    fr = E.h_out;
-    froff = h_fo;
-  }
-
+  Framed fr;
+  if (const int rv = frame_literals(engine(), nblocks, B, stream, &fr)) return fail_batch(rv);
   ph.mark("gpu");
-  // ---- pass 2: each block's wire size, placement in block order, then the
-  // bytes (representation bytes and framed literals, in order)
-  std::vector<size_t> need(nblocks, 0);
-  parallel_for(nblocks, 256, [&](size_t i) {
-    size_t n = 0;
-    for (const Piece &pc : pieces[i]) {
-      n += pc.bytes.size();
-      for (int j = 0; j < 2; ++j)
-        if (pc.lit[j] >= 0) {
-          const uint32_t g = litbase[i] + (uint32_t)pc.lit[j];
-          n += froff[g + 1] - froff[g];
-        }
-    }
-    need[i] = n;
-  });
-  size_t o = 0;
-  int ret = 0;
-  out_off[0] = 0;
-  for (uint32_t i = 0; i < nblocks; ++i) {
-    if (block_status[i] == 0 && deflaters[i]->bad) {
-      // an earlier block of this deflater ran out of room in this call:
-      // later ones fail as nghttp2_hd_deflate_hd_bufs does (:1475-1477)
-      block_status[i] = NGHTTP2_AMD_ERR_HEADER_COMP;
-    } else if (block_status[i] == 0 && (o + need[i] > out_cap || o + need[i] > UINT32_MAX)) {
-      // INSUFF_BUFSIZE in nghttp2_hd_deflate_hd2 (:1546-1547); the deflater turns bad
-      block_status[i] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
-      deflaters[i]->bad = true;
-      ret = NGHTTP2_AMD_ERR_BUFFER_ERROR;
-    } else if (block_status[i] == 0) {
-      block_status[i] = (int32_t)need[i];
-      o += need[i];
-    }
-    out_off[i + 1] = (uint32_t)o;
-  }
-  parallel_for(nblocks, 256, [&](size_t i) {
-    if (block_status[i] < 0) return;
-    uint8_t *w = out + out_off[i];
-    for (const Piece &pc : pieces[i]) {
-      memcpy(w, pc.bytes.data(), pc.bytes.size());
-      w += pc.bytes.size();
-      for (int j = 0; j < 2; ++j) {
-        if (pc.lit[j] < 0) continue;
-        const uint32_t g = litbase[i] + (uint32_t)pc.lit[j];
-        const uint32_t a = froff[g], b = froff[g + 1];
-        memcpy(w, fr + a, b - a);
-        w += b - a;
-      }
-    }
-  });
+  const int ret = place_wire(deflaters, nblocks, B, fr, out, out_cap, out_off, block_status);
   ph.mark("wire");
   return ret;
 }

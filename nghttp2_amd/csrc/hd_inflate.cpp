@@ -19,44 +19,24 @@
 // add_hd_table_incremental (:1130-1195), and the sticky bad state (:1932).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
 #include <mutex>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_host.h"
 #include "host_threads.h"
 
 namespace {
 
+using namespace hdhost;  // the static table, hip_ok, DevBuf / PinnedBuf
+const char *const kLayer = "inflate";  // (in hip_ok's messages)
 const uint32_t kMaxNv = 65536;         // NGHTTP2_HD_MAX_NV
-const uint32_t kEntryOverhead = 32;    // NGHTTP2_HD_ENTRY_OVERHEAD
 const uint32_t kDefaultTable = 4096;   // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
-const uint32_t kStaticLen = 61;
-
-// RFC 7541 Appendix A
-const char *const kStatic[kStaticLen][2] = {
-    {":authority", ""}, {":method", "GET"}, {":method", "POST"}, {":path", "/"},
-    {":path", "/index.html"}, {":scheme", "http"}, {":scheme", "https"}, {":status", "200"},
-    {":status", "204"}, {":status", "206"}, {":status", "304"}, {":status", "400"},
-    {":status", "404"}, {":status", "500"}, {"accept-charset", ""},
-    {"accept-encoding", "gzip, deflate"}, {"accept-language", ""}, {"accept-ranges", ""},
-    {"accept", ""}, {"access-control-allow-origin", ""}, {"age", ""}, {"allow", ""},
-    {"authorization", ""}, {"cache-control", ""}, {"content-disposition", ""},
-    {"content-encoding", ""}, {"content-language", ""}, {"content-length", ""},
-    {"content-location", ""}, {"content-range", ""}, {"content-type", ""}, {"cookie", ""},
-    {"date", ""}, {"etag", ""}, {"expect", ""}, {"expires", ""}, {"from", ""}, {"host", ""},
-    {"if-match", ""}, {"if-modified-since", ""}, {"if-none-match", ""}, {"if-range", ""},
-    {"if-unmodified-since", ""}, {"last-modified", ""}, {"link", ""}, {"location", ""},
-    {"max-forwards", ""}, {"proxy-authenticate", ""}, {"proxy-authorization", ""},
-    {"range", ""}, {"referer", ""}, {"refresh", ""}, {"retry-after", ""}, {"server", ""},
-    {"set-cookie", ""}, {"strict-transport-security", ""}, {"transfer-encoding", ""},
-    {"user-agent", ""}, {"vary", ""}, {"via", ""}, {"www-authenticate", ""}};
 
 // The dynamic table (lib/nghttp2_hd.c hd_ringbuf + nghttp2_hd_entry, restated
 // without a heap object per entry): entry descriptors in a power-of-two ring,
@@ -168,6 +148,16 @@ struct nghttp2_amd_hd_inflater {
     max_vl = std::max(max_vl, vl);
   }
   size_t max_index() const { return table.count + kStaticLen; }  // get_max_index
+  // entry idx of the index space, 0-based (idx < max_index()): static, then
+  // the dynamic table newest first
+  void entry(size_t idx, const char **n, size_t *nl, const char **v, size_t *vl) const {
+    if (idx < kStaticLen) return static_entry((uint32_t)idx, n, nl, v, vl);
+    const DynTable::Ent &e = table.newest(idx - kStaticLen);
+    *n = (const char *)table.name(e);
+    *nl = e.nl;
+    *v = (const char *)table.value(e);
+    *vl = e.vl;
+  }
 };
 
 namespace {
@@ -249,16 +239,10 @@ struct alignas(128) BlockOut {
 
 struct Engine {
   std::mutex mu;
-  uint8_t *h_pool = nullptr;  // pinned: Huffman literals in
-  size_t h_cap = 0;
-  uint8_t *h_out = nullptr;  // pinned: decoded literals out
-  size_t o_cap = 0;
-  uint32_t *h_meta = nullptr;  // pinned: offsets in, slots + status out
-  size_t m_cap = 0;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  uint32_t *d_off = nullptr, *d_slot = nullptr;
-  int32_t *d_st = nullptr;
-  size_t din_cap = 0, dout_cap = 0, dn_cap = 0;
+  PinnedBuf h_pool;  // Huffman literals in
+  PinnedBuf h_out;   // decoded literals out
+  PinnedBuf h_meta;  // uint32: offsets in, then slots and status out ((nh + 1) each)
+  DevBuf d_in, d_out, d_meta;  // their device copies (the modes that copy)
   std::vector<BlockOut> outs;
   // pass 1 state, kept across calls (under mu)
   std::vector<Block> bl;
@@ -272,38 +256,6 @@ struct Engine {
 Engine &engine() {
   static Engine e;
   return e;
-}
-
-bool hip_ok(hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  fprintf(stderr, "nghttp2_amd_hd (inflate): %s: %s\n", what, hipGetErrorString(e));
-  return false;
-}
-
-// (pinned, mapped into the device's address space and coherent: the
-// zero-copy decode reads and writes these pools directly; mapped = false: a
-// pool the device only reaches by DMA copies, plain pinned memory)
-bool grow_host(void **p, size_t *cap, size_t need, bool mapped = true) {
-  if (need <= *cap) return true;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  // (coherent: a non-coherent mapping measured the same, round 5,
-  // profiles/r05/inflate/pin_modes.log)
-  if (!hip_ok(hipHostMalloc(p, need, mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault),
-              "hipHostMalloc"))
-    return false;
-  *cap = need;
-  return true;
-}
-bool grow_dev(void **p, size_t *cap, size_t need) {
-  if (need <= *cap) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (!hip_ok(hipMalloc(p, need), "hipMalloc")) return false;
-  *cap = need;
-  return true;
 }
 
 // Pass 1: representations and literal extents of one block
@@ -371,32 +323,6 @@ struct LitSrc {
   }
 };
 
-size_t static_len(uint32_t idx, int which) {
-  static size_t lens[kStaticLen][2];
-  static bool init = [] {
-    for (uint32_t i = 0; i < kStaticLen; ++i) {
-      lens[i][0] = strlen(kStatic[i][0]);
-      lens[i][1] = strlen(kStatic[i][1]);
-    }
-    return true;
-  }();
-  (void)init;
-  return lens[idx][which];
-}
-// the static table's longest name and value
-size_t static_max(int which) {
-  static const size_t m[2] = {[] {
-                                size_t x = 0;
-                                for (uint32_t i = 0; i < kStaticLen; ++i) x = std::max(x, static_len(i, 0));
-                                return x;
-                              }(),
-                              [] {
-                                size_t x = 0;
-                                for (uint32_t i = 0; i < kStaticLen; ++i) x = std::max(x, static_len(i, 1));
-                                return x;
-                              }()};
-  return m[which];
-}
 // What one dynamic-table reference of block b can emit (name + value): any
 // entry it can reach is one in the table now or one the block inserts, whose
 // name is a literal's, a static entry's or an older entry's and whose value
@@ -406,9 +332,17 @@ size_t static_max(int which) {
 // block with a dynamic reference through the slow copy-and-replay path).
 uint64_t dyn_ref_bound(const nghttp2_amd_hd_inflater *c, uint64_t lit_name, uint64_t lit_val) {
   const uint64_t lim = std::min<uint64_t>(std::max<size_t>({64u, c->settings_max, c->bufsize_max}), UINT32_MAX);
-  const uint64_t n = std::max<uint64_t>({c->max_nl, static_max(0), lit_name});
-  const uint64_t v = std::max<uint64_t>({c->max_vl, static_max(1), lit_val});
+  const uint64_t n = std::max<uint64_t>({c->max_nl, kStaticLens.max[0], lit_name});
+  const uint64_t v = std::max<uint64_t>({c->max_vl, kStaticLens.max[1], lit_val});
   return std::min(lim, n + v);
+}
+// (the bounds saturate at UINT64_MAX: a table limit near SIZE_MAX must not
+// wrap them)
+uint64_t sat_add(uint64_t a, uint64_t b) { return a > UINT64_MAX - b ? UINT64_MAX : a + b; }
+// A block's arena bound: its own bytes plus its dynamic-table references at
+// ref_max each (dyn_ref_bound).
+uint64_t block_ar_bound(const Block &b, uint64_t ref_max) {
+  return sat_add(b.ar, b.ndyn && ref_max > UINT64_MAX / b.ndyn ? UINT64_MAX : b.ndyn * ref_max);
 }
 
 // Pass 2 for one block against its inflater (in order within a connection):
@@ -475,23 +409,6 @@ struct DirectSink {
 template <class Sink>
 void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, Sink &out) {
   out.begin();
-  auto emit = [&](const char *n, size_t nl, const char *v, size_t vl, uint8_t flags) {
-    out.emit(n, nl, v, vl, flags);
-  };
-  auto entry = [&](uint32_t idx, const char **n, size_t *nl, const char **v, size_t *vl) {
-    if (idx < kStaticLen) {
-      *n = kStatic[idx][0];
-      *nl = static_len(idx, 0);
-      *v = kStatic[idx][1];
-      *vl = static_len(idx, 1);
-    } else {
-      const DynTable::Ent &e = inf->table.newest(idx - kStaticLen);
-      *n = (const char *)inf->table.name(e);
-      *nl = e.nl;
-      *v = (const char *)inf->table.value(e);
-      *vl = e.vl;
-    }
-  };
   bool ok = !inf->bad;
   bool head = true;  // size updates only at the head of a block
   for (size_t k = 0; ok && k < b.ops.size(); ++k) {
@@ -519,8 +436,8 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
         ok = false;
         break;
       }
-      entry(op.value - 1, &n, &nl, &v, &vl);
-      emit(n, nl, v, vl, 0);
+      inf->entry(op.value - 1, &n, &nl, &v, &vl);
+      out.emit(n, nl, v, vl, 0);
       continue;
     }
     if (op.new_name) {  // hd_inflate_commit_newname
@@ -535,14 +452,14 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       }
       const char *v0;
       size_t vl0;
-      entry(op.value - 1, &n, &nl, &v0, &vl0);
+      inf->entry(op.value - 1, &n, &nl, &v0, &vl0);
     }
     if (!ls.get(op.val, &v, &vl)) {
       ok = false;
       break;
     }
     const uint8_t flags = op.no_index ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
-    emit(n, nl, v, vl, flags);
+    out.emit(n, nl, v, vl, flags);
     if (op.index_required)  // the table copies the field just emitted
       inf->add(out.last_name(), nl, out.last_value(), vl);
   }
@@ -556,6 +473,365 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
   } else {
     out.finish(out.count());
   }
+}
+
+// ---- the phases of nghttp2_amd_hd_inflate_blocks, each named after the trace mark that closes it
+using nghttp2_amd_host::parallel_for;
+using nghttp2_amd_host::Phases;
+
+// The caller's output buffers.
+struct Dest {
+  nghttp2_amd_hd_nv *nva;
+  size_t nva_cap, *nva_used;
+  uint8_t *arena;
+  size_t arena_cap, *arena_used;
+  int32_t *block_status;
+};
+
+// The parts of a parsed block's output bound: a field per representation,
+// its name and value NUL-terminated; a literal's bytes (a Huffman one at its
+// decode bound); a static-table reference at its entry's own length, a
+// dynamic one counted (dyn_ref_bound bounds it at replay).
+void bound_block(Block &b) {
+  b.nv = b.ar = b.ndyn = b.lit_name = b.lit_val = 0;
+  auto lit_len = [](const Lit &l) -> uint64_t {
+    return l.huff < 0 ? (uint64_t)l.len : (uint64_t)l.len * 8u / 5u + 1u;
+  };
+  auto ref = [&](uint32_t idx, bool name_only) {
+    if (idx >= 1 && idx <= kStaticLen)
+      b.ar += kStaticLens.len[idx - 1][0] + (name_only ? 0 : kStaticLens.len[idx - 1][1]);
+    else
+      ++b.ndyn;
+  };
+  for (const Op &op : b.ops) {
+    if (op.kind == Op::SIZE) continue;
+    ++b.nv;
+    b.ar += 2u;
+    if (op.kind == Op::INDEXED) {
+      ref(op.value, false);
+    } else {
+      if (op.new_name) {
+        b.ar += lit_len(op.name);
+        b.lit_name = std::max(b.lit_name, lit_len(op.name));
+      } else {
+        ref(op.value, true);
+      }
+      b.ar += lit_len(op.val);
+      b.lit_val = std::max(b.lit_val, lit_len(op.val));
+    }
+  }
+}
+
+// "parse blocks" -- pass 1: every block parsed and bounded, its Huffman
+// literals counted (stateless: one task per block).  The engine's per-block
+// buffers are kept across calls, so a warm call allocates nothing here; a call
+// far below an earlier large batch releases the surplus (a high-water mark of 2x +
+// 4096 blocks), so one large batch does not pin its footprint for the process's life.
+void parse_blocks(Engine &E, uint32_t nblocks, const uint8_t *const *blocks, const size_t *block_lens) {
+  auto trim = [nblocks](auto &v) {
+    if (v.size() > 2u * (size_t)nblocks + 4096u) {
+      v.resize(nblocks);
+      v.shrink_to_fit();
+    }
+  };
+  trim(E.bl), trim(E.outs);
+  if (E.bl.size() < nblocks) E.bl.resize(nblocks);
+  E.nhuff.assign(nblocks + 1, 0);   // Huffman literals per block, then prefix
+  E.hbytes.assign(nblocks + 1, 0);  // their bytes per block, then prefix
+  parallel_for(nblocks, 64, [&](size_t i) {
+    // a malformed block keeps the representations before the error: the
+    // reference emits those fields before it fails
+    Block &b = E.bl[i];
+    b.parse_ok = parse_block(blocks[i], block_lens[i], b);
+    uint32_t c = 0;
+    uint64_t by = 0;
+    for (const Op &op : b.ops)
+      if (op.kind == Op::LITERAL) {
+        if (op.name.huff == 0) ++c, by += op.name.len;
+        if (op.val.huff == 0) ++c, by += op.val.len;
+      }
+    E.nhuff[i + 1] = c;
+    E.hbytes[i + 1] = by;
+    bound_block(b);
+  });
+}
+
+// "number+copy": each block numbers its Huffman literals and copies their bytes into the
+// pinned input pool, in one parallel pass (round 5; before: numbering, then a separate gather).
+// (by-value arguments: the loop reads nothing that may share a line with parallel_for's counter)
+void number_block(Block &b, uint32_t k, uint32_t o, uint8_t *hp, uint32_t *hoff) {
+  for (Op &op : b.ops) {
+    if (op.kind != Op::LITERAL) continue;
+    if (op.name.huff == 0) {
+      op.name.huff = (int32_t)k;
+      memcpy(hp + o, op.name.p, op.name.len);
+      o += op.name.len;
+      hoff[++k] = o;
+    }
+    if (op.val.huff == 0) {
+      op.val.huff = (int32_t)k;
+      memcpy(hp + o, op.val.p, op.val.len);
+      o += op.val.len;
+      hoff[++k] = o;
+    }
+  }
+}
+void number_and_copy(Engine &E, uint32_t nblocks) {
+  E.hoff[0] = 0;
+  parallel_for(nblocks, 64, [&E](size_t i) {
+    number_block(E.bl[i], E.nhuff[i], (uint32_t)E.hbytes[i], E.h_pool.as<uint8_t>(), E.hoff.data());
+  });
+}
+
+// NGHTTP2_AMD_INFLATE_ZC, read once per process (tests/test_inflate_zc.py
+// runs the RFC and random-connection cases under each mode in its own
+// process).  2, the default: the kernel reads the literals and offsets
+// straight from the mapped pinned pools (zero-copy in: no H2D copies or their
+// launch latencies) and its output is copied out -- DMA lands it in whole lines.
+// 1: the output too goes through the mapped pool.  0: explicit copies both ways.
+int zc_mode() {
+  static const int mode = [] {
+    const char *e = getenv("NGHTTP2_AMD_INFLATE_ZC");
+    return e && (atoi(e) == 0 || atoi(e) == 1) ? atoi(e) : 2;
+  }();
+  return mode;
+}
+
+// "pools", "number+copy", "gpu issued": every Huffman literal of the batch
+// in one decode, queued on the caller's stream.  The pinned pools are sized
+// first, so number_and_copy can fill the input pool in place.  *ls says where
+// replay finds the decoded literals once the stream has been waited for.
+int stage_decode(Engine &E, uint32_t nblocks, void *stream, Phases &ph, LitSrc *ls) {
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    E.nhuff[i + 1] += E.nhuff[i];
+    E.hbytes[i + 1] += E.hbytes[i];
+  }
+  const uint32_t nh = E.nhuff[nblocks];
+  const uint64_t hb = E.hbytes[nblocks];
+  // uint32 offsets into the batch's literal pool (and uint32 decode slots):
+  // a batch past them is refused before any connection state changes
+  if (hb > UINT32_MAX || (nh && nghttp2_amd_hd_huff_decode_bound(hb, nh) > UINT32_MAX))
+    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  if (E.hoff.size() < (size_t)nh + 1) E.hoff.resize((size_t)nh + 1);
+  const int mode = zc_mode();
+  const bool zero_copy = mode == 1;
+  const size_t in_bytes = ((size_t)hb + 15u) / 16u * 16u + 16u;
+  const size_t out_bytes = nh ? nghttp2_amd_hd_huff_decode_bound(hb, nh) : 0;
+  const size_t slots = (size_t)nh + 1u, meta = 3u * slots * sizeof(uint32_t);
+  // (the output pool is a D2H copy target unless the kernel writes it
+  // through the mapping, mode 1; the input pools are mapped unless mode 0;
+  // mode 2 needs no device copy of the input)
+  if (nh && (!E.h_pool.reserve(in_bytes, kLayer, mode != 0) || !E.h_out.reserve(out_bytes, kLayer, zero_copy) ||
+             !E.h_meta.reserve(meta, kLayer, mode != 0) ||
+             (!zero_copy && ((mode == 0 && !E.d_in.reserve(in_bytes, kLayer)) ||
+                             !E.d_out.reserve(out_bytes, kLayer) || !E.d_meta.reserve(meta, kLayer)))))
+    return NGHTTP2_AMD_ERR_NOMEM;
+  ph.mark("pools");
+  number_and_copy(E, nblocks);
+  ph.mark("number+copy");
+  *ls = LitSrc{nullptr, nullptr, nullptr};
+  if (!nh) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t *const h_meta = E.h_meta.as<uint32_t>();
+  memset(E.h_pool.as<uint8_t>() + hb, 0, in_bytes - hb);
+  memcpy(h_meta, E.hoff.data(), slots * sizeof(uint32_t));
+  // a failure after the first copy or launch is queued drains the stream
+  // before returning: GPU work still in flight must not land in the pinned
+  // pools after the next call has filled them
+  auto drain = [st](int rv) {
+    (void)hipStreamSynchronize(st);
+    return rv;
+  };
+  // the pinned pools as the device sees them: input and offsets unless mode
+  // 0, the output in mode 1
+  void *m_in = nullptr, *m_out = nullptr, *m_meta = nullptr;
+  if (mode != 0 && (hipHostGetDevicePointer(&m_in, E.h_pool.p, 0) != hipSuccess ||
+                    (zero_copy && hipHostGetDevicePointer(&m_out, E.h_out.p, 0) != hipSuccess) ||
+                    hipHostGetDevicePointer(&m_meta, E.h_meta.p, 0) != hipSuccess))
+    return NGHTTP2_AMD_ERR_FATAL;
+  const uint8_t *src = mode != 0 ? (const uint8_t *)m_in : E.d_in.as<uint8_t>();
+  const uint32_t *src_off = mode != 0 ? (const uint32_t *)m_meta : E.d_meta.as<uint32_t>();
+  uint8_t *dst = zero_copy ? (uint8_t *)m_out : E.d_out.as<uint8_t>();
+  uint32_t *d_slot = (zero_copy ? (uint32_t *)m_meta : E.d_meta.as<uint32_t>()) + slots;
+  int32_t *d_st = (int32_t *)(d_slot + slots);
+  if (mode == 0 &&
+      (hipMemcpyAsync(E.d_in.p, E.h_pool.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+       hipMemcpyAsync(E.d_meta.p, h_meta, slots * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess))
+    return drain(NGHTTP2_AMD_ERR_FATAL);
+  const int rv = nghttp2_amd_hd_huff_decode_batch_auto(src, src_off, nh, hb, dst, out_bytes, d_slot, d_st,
+                                                       nullptr, nullptr, stream);
+  if (rv) return drain(rv);
+  uint32_t *h_slot = h_meta + slots;
+  int32_t *h_st = (int32_t *)(h_slot + slots);
+  if (!zero_copy &&
+      (hipMemcpyAsync(E.h_out.p, dst, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(h_slot, d_slot, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess))
+    return drain(NGHTTP2_AMD_ERR_FATAL);
+  *ls = LitSrc{E.h_out.as<uint8_t>(), h_slot, h_st};
+  return 0;
+}
+
+// "group": the batch's blocks per connection, in batch order -- conns, and
+// connection c's blocks corder[cstart[c] .. cstart[c + 1]).  A connection is
+// numbered at its first block by a stamp in the inflater, no hash lookups.
+void group_by_connection(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks) {
+  std::vector<uint32_t> &cstart = E.cstart, &corder = E.corder;
+  auto &conns = E.conns;
+  conns.clear();
+  const uint64_t gen = ++E.gen;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    nghttp2_amd_hd_inflater *c = inflaters[i];
+    if (c->batch_gen != gen) {
+      c->batch_gen = gen;
+      c->batch_conn = (uint32_t)conns.size();
+      conns.push_back(c);
+    }
+  }
+  cstart.assign(conns.size() + 1, 0);
+  corder.resize(nblocks);
+  for (uint32_t i = 0; i < nblocks; ++i) ++cstart[inflaters[i]->batch_conn + 1];
+  for (size_t c = 0; c < conns.size(); ++c) cstart[c + 1] += cstart[c];
+  std::vector<uint32_t> fill(cstart.begin(), cstart.end() - 1);
+  for (uint32_t i = 0; i < nblocks; ++i) corder[fill[inflaters[i]->batch_conn]++] = i;
+}
+
+// "bound": whether an upper bound of the batch's output (pass 1's per-block
+// parts, a dynamic-table reference at dyn_ref_bound) can pass the caller's
+// caps.  Only then can the batch be cut, so only then are the tables snapshotted.
+bool may_cut(const Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks, const Dest &d) {
+  std::vector<uint64_t> run_ln(E.conns.size(), 0), run_lv(E.conns.size(), 0);
+  uint64_t nv_bound = 0, ar_bound = 0;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    const nghttp2_amd_hd_inflater *c = inflaters[i];
+    const Block &b = E.bl[i];
+    // (a connection's earlier blocks of the batch insert before this one:
+    // their literals count too -- the running maxima)
+    const uint32_t cn = c->batch_conn;
+    run_ln[cn] = std::max(run_ln[cn], b.lit_name);
+    run_lv[cn] = std::max(run_lv[cn], b.lit_val);
+    const uint64_t ar_b = block_ar_bound(b, dyn_ref_bound(c, run_ln[cn], run_lv[cn]));
+    nv_bound += b.nv;
+    ar_bound = sat_add(ar_bound, ar_b);
+    if (nv_bound > d.nva_cap || ar_bound > d.arena_cap) return true;
+  }
+  return false;
+}
+
+// One replayed block's fields into the caller's field array at nv_base and arena at ar_base.
+void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_base, nghttp2_amd_hd_nv *nva,
+                 uint8_t *arena) {
+  const uint32_t ab = (uint32_t)ar_base;
+  if (!o.bytes.empty()) memcpy(arena + ab, o.bytes.data(), o.bytes.size());
+  nghttp2_amd_hd_nv *d = nva + nv_base;
+  for (const Rec &r : o.recs)
+    *d++ = nghttp2_amd_hd_nv{block, ab + r.name_off, r.name_len, ab + r.value_off, r.value_len, r.flags};
+}
+
+// "replay direct" -- pass 2 for a batch of one connection (a serial replay
+// anyway): fields straight into the caller's arena and array in block order,
+// no per-block buffers, no placement pass (round 5: config 1's 1,000 blocks
+// of one connection).  A block whose own output bound may pass the caps is
+// replayed into a scratch buffer from a copy of the table, and placed if it
+// fits, else the table is restored and the batch cut there.
+int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, void *stream, Phases &ph) {
+  if (ls.st && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
+  ph.mark("gpu wait");
+  nghttp2_amd_hd_inflater *c = E.conns[0];
+  DirectSink ds{d.arena, d.nva, d.block_status};
+  uint32_t cut = nblocks;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    const Block &b = E.bl[i];
+    // (bounds from the table as it is now: the earlier blocks' inserts are
+    // in it, and in max_nl / max_vl)
+    const uint64_t ar_b = block_ar_bound(b, dyn_ref_bound(c, b.lit_name, b.lit_val));
+    ds.block = i;
+    if (ds.nv + b.nv <= d.nva_cap && ar_b <= d.arena_cap - ds.ar) {
+      replay_block(c, b, ls, ds);
+      continue;
+    }
+    nghttp2_amd_hd_inflater keep = *c;
+    BlockOut scratch;
+    BlockSink bs{scratch};
+    replay_block(c, b, ls, bs);
+    if (ds.nv + scratch.recs.size() > d.nva_cap || scratch.bytes.size() > d.arena_cap - ds.ar) {
+      *c = std::move(keep);
+      cut = i;
+      break;
+    }
+    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena);
+    ds.nv += scratch.recs.size();
+    ds.ar += scratch.bytes.size();
+    d.block_status[i] = scratch.status;
+  }
+  for (uint32_t j = cut; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+  ph.mark("replay direct");
+  *d.nva_used = ds.nv;
+  *d.arena_used = ds.ar;
+  return cut < nblocks ? NGHTTP2_AMD_ERR_BUFFER_ERROR : 0;
+}
+
+// "replay", "place" -- pass 2 for several connections: each connection's
+// blocks in batch order against its table (one task per connection), fields
+// into per-block buffers, then placed in block order.  A batch that outgrows
+// the caller's buffers is cut at the first block that does not fit, and the tables
+// replayed up to there from snapshots (a copy of every table, if cut_possible).
+int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks, const LitSrc &ls,
+                   const Dest &d, bool cut_possible, void *stream, Phases &ph) {
+  const std::vector<nghttp2_amd_hd_inflater *> &conns = E.conns;
+  std::vector<nghttp2_amd_hd_inflater> snap;
+  if (cut_possible) {
+    snap.reserve(conns.size());
+    for (auto *c : conns) snap.push_back(*c);
+  }
+  if (ls.st && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
+  ph.mark("gpu wait");
+  // per-block field buffers, kept across calls (under the engine's lock):
+  // replay allocates only while they grow
+  std::vector<BlockOut> &outs = E.outs;
+  if (outs.size() < nblocks) outs.resize(nblocks);
+  parallel_for(conns.size(), 1, [&](size_t c) {
+    for (uint32_t j = E.cstart[c]; j < E.cstart[c + 1]; ++j) {
+      BlockSink bs{outs[E.corder[j]]};
+      replay_block(conns[c], E.bl[E.corder[j]], ls, bs);
+    }
+  });
+  ph.mark("replay");
+  std::vector<size_t> nv_base(nblocks + 1, 0), ar_base(nblocks + 1, 0);
+  uint32_t cut = nblocks;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    nv_base[i + 1] = nv_base[i] + outs[i].recs.size();
+    ar_base[i + 1] = ar_base[i] + outs[i].bytes.size();
+    if (nv_base[i + 1] > d.nva_cap || ar_base[i + 1] > d.arena_cap) {
+      cut = i;
+      break;
+    }
+  }
+  if (cut < nblocks && !cut_possible) {
+    // the bound missed an output that fits no cap: the tables are past the
+    // cut with no snapshot to restore, so the batch fails and its inflaters
+    // turn bad (an internal error, never expected)
+    for (auto *c : conns) c->bad = true;
+    for (uint32_t j = 0; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_FATAL;
+    *d.nva_used = 0;
+    *d.arena_used = 0;
+    return NGHTTP2_AMD_ERR_FATAL;
+  }
+  if (cut < nblocks) {  // restore, then re-apply the blocks before the cut
+    for (size_t c = 0; c < conns.size(); ++c) *conns[c] = std::move(snap[c]);
+    BlockOut scratch;
+    BlockSink ss{scratch};
+    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], E.bl[i], ls, ss);
+    for (uint32_t j = cut; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+  }
+  parallel_for(cut, 256, [&](size_t i) {
+    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena);
+    d.block_status[i] = outs[i].status;
+  });
+  ph.mark("place");
+  *d.nva_used = nv_base[cut];
+  *d.arena_used = ar_base[cut];
+  return cut < nblocks ? NGHTTP2_AMD_ERR_BUFFER_ERROR : 0;
 }
 
 }  // namespace
@@ -638,19 +914,10 @@ int nghttp2_amd_hd_inflate_get_table_entry(nghttp2_amd_hd_inflater *inf, size_t 
                                            const uint8_t **name, size_t *namelen,
                                            const uint8_t **value, size_t *valuelen) {
   if (!inf || idx == 0 || idx > inf->max_index()) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  --idx;
-  if (idx < kStaticLen) {
-    *name = (const uint8_t *)kStatic[idx][0];
-    *namelen = strlen(kStatic[idx][0]);
-    *value = (const uint8_t *)kStatic[idx][1];
-    *valuelen = strlen(kStatic[idx][1]);
-  } else {
-    const DynTable::Ent &e = inf->table.newest(idx - kStaticLen);
-    *name = inf->table.name(e);
-    *namelen = e.nl;
-    *value = inf->table.value(e);
-    *valuelen = e.vl;
-  }
+  const char *n, *v;
+  inf->entry(idx - 1, &n, namelen, &v, valuelen);
+  *name = (const uint8_t *)n;
+  *value = (const uint8_t *)v;
   return 0;
 }
 
@@ -675,386 +942,24 @@ int nghttp2_amd_hd_inflate_blocks(nghttp2_amd_hd_inflater *const *inflaters, uin
   for (uint32_t i = 0; i < nblocks; ++i)
     if (!inflaters[i] || (!blocks[i] && block_lens[i])) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
 
-  // ---- pass 1: parse every block (stateless: one task per block); the
-  // engine's buffers are reused across calls, so a warm call allocates
-  // nothing here
-  using nghttp2_amd_host::parallel_for;
   nghttp2_amd_host::Pool::CallScope scope;  // workers spin between this call's phases only
-  nghttp2_amd_host::Phases ph("inflate");
+  Phases ph("inflate");
   std::lock_guard<std::mutex> guard(engine().mu);
   Engine &E = engine();
-  // the per-block buffers are kept across calls so a warm call allocates
-  // nothing; a call far below an earlier large batch releases the surplus
-  // (a high-water mark of 2x + 4096 blocks), so one large batch does not pin
-  // its parse and output footprint for the life of the process
-  auto trim = [nblocks](auto &v) {
-    if (v.size() > 2u * (size_t)nblocks + 4096u) {
-      v.resize(nblocks);
-      v.shrink_to_fit();
-    }
-  };
-  trim(E.bl);
-  trim(E.outs);
-  if (E.bl.size() < nblocks) E.bl.resize(nblocks);
-  E.nhuff.assign(nblocks + 1, 0);  // Huffman literals per block, then prefix
-  E.hbytes.assign(nblocks + 1, 0);  // their bytes per block, then prefix
-  std::vector<Block> &bl = E.bl;
-  std::vector<uint32_t> &nhuff = E.nhuff;
-  parallel_for(nblocks, 64, [&](size_t i) {
-    // a malformed block keeps the representations before the error: the
-    // reference emits those fields before it fails
-    bl[i].parse_ok = parse_block(blocks[i], block_lens[i], bl[i]);
-    uint32_t c = 0;
-    uint64_t by = 0;
-    for (const Op &op : bl[i].ops)
-      if (op.kind == Op::LITERAL) {
-        if (op.name.huff == 0) ++c, by += op.name.len;
-        if (op.val.huff == 0) ++c, by += op.val.len;
-      }
-    nhuff[i + 1] = c;
-    E.hbytes[i + 1] = by;
-    // the block's output bound (below): a field per representation, its name
-    // and value NUL-terminated; a literal's bytes (a Huffman one at its
-    // decode bound); a static-table reference at its entry's own length, a
-    // dynamic one counted (the connection's table limit bounds it)
-    uint64_t nv = 0, ar = 0, nd = 0;
-    auto lit_len = [](const Lit &l) -> uint64_t {
-      return l.huff < 0 ? (uint64_t)l.len : (uint64_t)l.len * 8u / 5u + 1u;
-    };
-    auto ref = [&](uint32_t idx, bool name_only) {
-      if (idx >= 1 && idx <= kStaticLen)
-        ar += static_len(idx - 1, 0) + (name_only ? 0 : static_len(idx - 1, 1));
-      else
-        ++nd;
-    };
-    uint64_t ln = 0, lv = 0;
-    for (const Op &op : bl[i].ops) {
-      if (op.kind == Op::SIZE) continue;
-      ++nv;
-      ar += 2u;
-      if (op.kind == Op::INDEXED) {
-        ref(op.value, false);
-      } else {
-        if (op.new_name) {
-          ar += lit_len(op.name);
-          ln = std::max(ln, lit_len(op.name));
-        } else {
-          ref(op.value, true);
-        }
-        ar += lit_len(op.val);
-        lv = std::max(lv, lit_len(op.val));
-      }
-    }
-    bl[i].lit_name = ln;
-    bl[i].lit_val = lv;
-    bl[i].nv = nv;
-    bl[i].ar = ar;
-    bl[i].ndyn = nd;
-  });
+  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status};
+  parse_blocks(E, nblocks, blocks, block_lens);
   ph.mark("parse blocks");
-  for (uint32_t i = 0; i < nblocks; ++i) {
-    nhuff[i + 1] += nhuff[i];
-    E.hbytes[i + 1] += E.hbytes[i];
-  }
-  const uint32_t nh = nhuff[nblocks];
-  // uint32 offsets into the batch's literal pool (and uint32 decode slots):
-  // a batch past them is refused before any connection state changes
-  if (E.hbytes[nblocks] > UINT32_MAX ||
-      (nh && nghttp2_amd_hd_huff_decode_bound(E.hbytes[nblocks], nh) > UINT32_MAX))
-    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  if (E.hoff.size() < (size_t)nh + 1) E.hoff.resize((size_t)nh + 1);
-  std::vector<uint32_t> &hoff = E.hoff;
-  // ---- GPU: every Huffman literal of the batch in one decode.  The pinned
-  // pools are sized first, so each block numbers its literals and copies
-  // their bytes into the pinned input pool in one parallel pass (round 5;
-  // before: numbering, then a separate gather over the literals).  By
-  // default the kernel reads the literals and offsets straight from the
-  // mapped pinned pools (zero-copy in: no H2D copies or their launch
-  // latencies) and its output is copied out;  NGHTTP2_AMD_INFLATE_ZC=1 also
-  // writes the output through the mapped pool, 0 copies both ways.
-  // (2: zero-copy in, the output copied out -- DMA lands it in whole lines)
-  // The mode is read once per process; tests/test_inflate_zc.py runs the
-  // RFC and random-connection cases under each mode in its own process.
-  static const int zc_mode = [] {
-    const char *e = getenv("NGHTTP2_AMD_INFLATE_ZC");
-    const int m = e ? atoi(e) : 2;
-    return m == 0 || m == 1 ? m : 2;
-  }();
-  const bool zero_copy = zc_mode == 1, zero_in = zc_mode == 2;
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t hb = E.hbytes[nblocks];
-  const size_t in_bytes = ((size_t)hb + 15u) / 16u * 16u + 16u;
-  const size_t out_bytes = nh ? nghttp2_amd_hd_huff_decode_bound(hb, nh) : 0;
-  const size_t meta = 3u * ((size_t)nh + 1u) * sizeof(uint32_t);
-  if (nh) {
-    // (the output pool is a D2H copy target unless the kernel writes it
-    // through the mapping, mode 1; the input pools are mapped unless mode 0)
-    if (!grow_host((void **)&E.h_pool, &E.h_cap, in_bytes, zc_mode != 0) ||
-        !grow_host((void **)&E.h_out, &E.o_cap, out_bytes, zero_copy) ||
-        !grow_host((void **)&E.h_meta, &E.m_cap, meta, zc_mode != 0))
-      return NGHTTP2_AMD_ERR_NOMEM;
-    if (!zero_copy && ((!zero_in && !grow_dev((void **)&E.d_in, &E.din_cap, in_bytes)) ||
-                       !grow_dev((void **)&E.d_out, &E.dout_cap, out_bytes) ||
-                       !grow_dev((void **)&E.d_off, &E.dn_cap, meta)))
-      return NGHTTP2_AMD_ERR_NOMEM;
-  }
-  ph.mark("pools");
-  hoff[0] = 0;
-  uint8_t *const hp = E.h_pool;
-  parallel_for(nblocks, 64, [&](size_t i) {  // each block numbers and places its literals
-    uint32_t k = nhuff[i];
-    uint32_t o = (uint32_t)E.hbytes[i];
-    for (Op &op : bl[i].ops) {
-      if (op.kind != Op::LITERAL) continue;
-      if (op.name.huff == 0) {
-        op.name.huff = (int32_t)k;
-        memcpy(hp + o, op.name.p, op.name.len);
-        o += op.name.len;
-        hoff[++k] = o;
-      }
-      if (op.val.huff == 0) {
-        op.val.huff = (int32_t)k;
-        memcpy(hp + o, op.val.p, op.val.len);
-        o += op.val.len;
-        hoff[++k] = o;
-      }
-    }
-  });
-
-  ph.mark("number+copy");
-  const uint8_t *dec = nullptr;
-  const uint32_t *slot = nullptr;
-  const int32_t *hst = nullptr;
-  if (nh) {
-    memset(E.h_pool + hb, 0, in_bytes - hb);
-    memcpy(E.h_meta, hoff.data(), (nh + 1) * sizeof(uint32_t));
-    uint32_t *h_slot = E.h_meta + (nh + 1);
-    int32_t *h_st = (int32_t *)(h_slot + (nh + 1));
-    // a failure after the first copy or launch is queued drains the stream
-    // before returning: GPU work still in flight must not land in the pinned
-    // pools after the next call has filled them
-    auto drain = [st](int rv) {
-      (void)hipStreamSynchronize(st);
-      return rv;
-    };
-    if (zero_copy) {
-      void *d_in = nullptr, *d_out = nullptr, *d_meta = nullptr;
-      if (hipHostGetDevicePointer(&d_in, E.h_pool, 0) != hipSuccess ||
-          hipHostGetDevicePointer(&d_out, E.h_out, 0) != hipSuccess ||
-          hipHostGetDevicePointer(&d_meta, E.h_meta, 0) != hipSuccess)
-        return NGHTTP2_AMD_ERR_FATAL;
-      uint32_t *d_off = (uint32_t *)d_meta;
-      int rv = nghttp2_amd_hd_huff_decode_batch_auto((const uint8_t *)d_in, d_off, nh, hb, (uint8_t *)d_out,
-                                                     out_bytes, d_off + (nh + 1),
-                                                     (int32_t *)(d_off + 2 * (nh + 1)), nullptr, nullptr,
-                                                     stream);
-      if (rv) return drain(rv);
-    } else {
-      E.d_slot = E.d_off + (nh + 1);
-      E.d_st = (int32_t *)(E.d_slot + (nh + 1));
-      const uint8_t *src = E.d_in;
-      const uint32_t *src_off = E.d_off;
-      if (zero_in) {  // the kernel reads the literals and offsets from the pinned pools
-        void *d_in = nullptr, *d_meta = nullptr;
-        if (hipHostGetDevicePointer(&d_in, E.h_pool, 0) != hipSuccess ||
-            hipHostGetDevicePointer(&d_meta, E.h_meta, 0) != hipSuccess)
-          return NGHTTP2_AMD_ERR_FATAL;
-        src = (const uint8_t *)d_in;
-        src_off = (const uint32_t *)d_meta;
-      } else if (hipMemcpyAsync(E.d_in, E.h_pool, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-                 hipMemcpyAsync(E.d_off, E.h_meta, (nh + 1) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                st) != hipSuccess) {
-        return drain(NGHTTP2_AMD_ERR_FATAL);
-      }
-      int rv = nghttp2_amd_hd_huff_decode_batch_auto(src, src_off, nh, hb, E.d_out, out_bytes,
-                                                     E.d_slot, E.d_st, nullptr, nullptr, stream);
-      if (rv) return drain(rv);
-      if (hipMemcpyAsync(E.h_out, E.d_out, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipMemcpyAsync(h_slot, E.d_slot, (nh + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                         st) != hipSuccess ||
-          hipMemcpyAsync(h_st, E.d_st, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st) !=
-              hipSuccess)
-        return drain(NGHTTP2_AMD_ERR_FATAL);
-    }
-    dec = E.h_out;
-    slot = h_slot;
-    hst = h_st;
-  }
-
+  LitSrc ls;
+  if (const int rv = stage_decode(E, nblocks, stream, ph, &ls)) return rv;
   ph.mark("gpu issued");
   // (the decode runs while the host groups the blocks by connection and
-  // bounds the output below; replay waits for it)
-  // ---- pass 2: each connection's blocks in batch order against its table
-  // (one task per connection), fields into per-block buffers
-  const LitSrc ls{dec, slot, hst};
-  // the batch's blocks per connection, in batch order (a connection is
-  // numbered at its first block by a stamp in the inflater, no hash lookups);
-  // the parallel region only reads the lists
-  std::vector<nghttp2_amd_hd_inflater *> &conns = E.conns;
-  conns.clear();
-  const uint64_t gen = ++E.gen;
-  for (uint32_t i = 0; i < nblocks; ++i) {
-    nghttp2_amd_hd_inflater *c = inflaters[i];
-    if (c->batch_gen != gen) {
-      c->batch_gen = gen;
-      c->batch_conn = (uint32_t)conns.size();
-      conns.push_back(c);
-    }
-  }
-  std::vector<uint32_t> &cstart = E.cstart, &corder = E.corder;
-  cstart.assign(conns.size() + 1, 0);
-  corder.resize(nblocks);
-  for (uint32_t i = 0; i < nblocks; ++i) ++cstart[inflaters[i]->batch_conn + 1];
-  for (size_t c = 0; c < conns.size(); ++c) cstart[c + 1] += cstart[c];
-  {
-    std::vector<uint32_t> fill(cstart.begin(), cstart.end() - 1);
-    for (uint32_t i = 0; i < nblocks; ++i) corder[fill[inflaters[i]->batch_conn]++] = i;
-  }
+  // bounds the output; replay waits for it)
+  group_by_connection(E, inflaters, nblocks);
   ph.mark("group");
-  // A batch that outgrows the caller's buffers is cut at the first block
-  // that does not fit, and the tables replayed up to there, from snapshots.
-  // The snapshots (a copy of every table) are taken only when an upper bound
-  // of the output (pass 1's per-block parts, a dynamic-table reference at
-  // dyn_ref_bound) can pass the caps.
-  bool may_cut = false;
-  {
-    std::vector<uint64_t> run_ln(conns.size(), 0), run_lv(conns.size(), 0);
-    // (saturating: a table limit near SIZE_MAX must not wrap the bound)
-    auto sat = [](uint64_t a, uint64_t b) -> uint64_t { return a > UINT64_MAX - b ? UINT64_MAX : a + b; };
-    uint64_t nv_bound = 0, ar_bound = 0;
-    for (uint32_t i = 0; i < nblocks && !may_cut; ++i) {
-      const nghttp2_amd_hd_inflater *c = inflaters[i];
-      const Block &b = bl[i];
-      // (a connection's earlier blocks of the batch insert before this one:
-      // their literals count too -- the running maxima below)
-      const uint32_t cn = c->batch_conn;
-      run_ln[cn] = std::max(run_ln[cn], b.lit_name);
-      run_lv[cn] = std::max(run_lv[cn], b.lit_val);
-      const uint64_t rm = dyn_ref_bound(c, run_ln[cn], run_lv[cn]);
-      const uint64_t dyn = b.ndyn && rm > UINT64_MAX / b.ndyn ? UINT64_MAX : b.ndyn * rm;
-      nv_bound += b.nv;
-      ar_bound = sat(ar_bound, sat(b.ar, dyn));
-      may_cut = nv_bound > nva_cap || ar_bound > arena_cap;
-    }
-  }
+  const bool cut_possible = may_cut(E, inflaters, nblocks, dest);
   ph.mark("bound");
-  if (conns.size() == 1) {
-    // one connection (a serial replay anyway): fields straight into the
-    // caller's arena and array in block order -- no per-block buffers, no
-    // placement pass (round 5: config 1's 1,000 blocks of one connection).
-    // A block whose own output bound may pass the caps is replayed into a
-    // scratch buffer from a copy of the table, and placed if it fits, else
-    // the table is restored and the batch cut there.
-    if (nh && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
-    ph.mark("gpu wait");
-    nghttp2_amd_hd_inflater *c = conns[0];
-    DirectSink ds{arena, nva, block_status};
-    uint32_t cut = nblocks;
-    for (uint32_t i = 0; i < nblocks; ++i) {
-      const Block &b = bl[i];
-      // (bounds from the table as it is now: the earlier blocks' inserts
-      // are in it, and in max_nl / max_vl)
-      const uint64_t rm = dyn_ref_bound(c, b.lit_name, b.lit_val);
-      const uint64_t ar_b = b.ndyn && rm > (UINT64_MAX - b.ar) / b.ndyn ? UINT64_MAX : b.ar + b.ndyn * rm;
-      ds.block = i;
-      if (ds.nv + b.nv <= nva_cap && ar_b <= arena_cap - ds.ar) {
-        replay_block(c, b, ls, ds);
-        continue;
-      }
-      nghttp2_amd_hd_inflater keep = *c;
-      BlockOut scratch;
-      BlockSink bs{scratch};
-      replay_block(c, b, ls, bs);
-      if (ds.nv + scratch.recs.size() > nva_cap || scratch.bytes.size() > arena_cap - ds.ar) {
-        *c = std::move(keep);
-        cut = i;
-        break;
-      }
-      if (!scratch.bytes.empty()) memcpy(arena + ds.ar, scratch.bytes.data(), scratch.bytes.size());
-      for (const Rec &r : scratch.recs) {
-        nghttp2_amd_hd_nv &d = nva[ds.nv++];
-        d.block = i;
-        d.name_off = (uint32_t)ds.ar + r.name_off;
-        d.name_len = r.name_len;
-        d.value_off = (uint32_t)ds.ar + r.value_off;
-        d.value_len = r.value_len;
-        d.flags = r.flags;
-      }
-      ds.ar += scratch.bytes.size();
-      block_status[i] = scratch.status;
-    }
-    for (uint32_t j = cut; j < nblocks; ++j) block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
-    ph.mark("replay direct");
-    *nva_used = ds.nv;
-    *arena_used = ds.ar;
-    return cut < nblocks ? NGHTTP2_AMD_ERR_BUFFER_ERROR : 0;
-  }
-  std::vector<nghttp2_amd_hd_inflater> snap;
-  if (may_cut) {
-    snap.reserve(conns.size());
-    for (auto *c : conns) snap.push_back(*c);
-  }
-  if (nh && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
-  ph.mark("gpu wait");
-  // per-block field buffers, kept across calls (under the engine's lock):
-  // replay allocates only while they grow
-  std::vector<BlockOut> &outs = E.outs;
-  if (outs.size() < nblocks) outs.resize(nblocks);
-  parallel_for(conns.size(), 1, [&](size_t c) {
-    for (uint32_t j = cstart[c]; j < cstart[c + 1]; ++j) {
-      BlockSink bs{outs[corder[j]]};
-      replay_block(conns[c], bl[corder[j]], ls, bs);
-    }
-  });
-
-  ph.mark("replay");
-  // ---- placement in block order
-  std::vector<size_t> nv_base(nblocks + 1, 0), ar_base(nblocks + 1, 0);
-  uint32_t cut = nblocks;
-  for (uint32_t i = 0; i < nblocks; ++i) {
-    nv_base[i + 1] = nv_base[i] + outs[i].recs.size();
-    ar_base[i + 1] = ar_base[i] + outs[i].bytes.size();
-    if (nv_base[i + 1] > nva_cap || ar_base[i + 1] > arena_cap) {
-      cut = i;
-      break;
-    }
-  }
-  if (cut < nblocks && !may_cut) {
-    // the bound missed an output that fits no cap: the tables are past the
-    // cut with no snapshot to restore, so the batch fails and its inflaters
-    // turn bad (an internal error, never expected)
-    for (auto *c : conns) c->bad = true;
-    for (uint32_t j = 0; j < nblocks; ++j) block_status[j] = NGHTTP2_AMD_ERR_FATAL;
-    *nva_used = 0;
-    *arena_used = 0;
-    return NGHTTP2_AMD_ERR_FATAL;
-  }
-  if (cut < nblocks) {  // restore, then re-apply the blocks before the cut
-    for (size_t c = 0; c < conns.size(); ++c) *conns[c] = std::move(snap[c]);
-    BlockOut scratch;
-    BlockSink ss{scratch};
-    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], bl[i], ls, ss);
-    for (uint32_t j = cut; j < nblocks; ++j) block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
-  }
-  parallel_for(cut, 256, [&](size_t i) {
-    const BlockOut &o = outs[i];
-    const uint32_t ab = (uint32_t)ar_base[i];
-    if (!o.bytes.empty()) memcpy(arena + ab, o.bytes.data(), o.bytes.size());
-    nghttp2_amd_hd_nv *d = nva + nv_base[i];
-    for (size_t k = 0; k < o.recs.size(); ++k) {
-      d[k].block = (uint32_t)i;
-      d[k].name_off = ab + o.recs[k].name_off;
-      d[k].name_len = o.recs[k].name_len;
-      d[k].value_off = ab + o.recs[k].value_off;
-      d[k].value_len = o.recs[k].value_len;
-      d[k].flags = o.recs[k].flags;
-    }
-    block_status[i] = o.status;
-  });
-  ph.mark("place");
-  *nva_used = nv_base[cut];
-  *arena_used = ar_base[cut];
-  return cut < nblocks ? NGHTTP2_AMD_ERR_BUFFER_ERROR : 0;
+  if (E.conns.size() == 1) return replay_direct(E, nblocks, ls, dest, stream, ph);
+  return replay_grouped(E, inflaters, nblocks, ls, dest, cut_possible, stream, ph);
 }
 
 }  // extern "C"

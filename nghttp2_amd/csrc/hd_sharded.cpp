@@ -18,7 +18,6 @@
 // shard's first 16-byte chunk, so src + off[i] lands in the shard's copy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -30,39 +29,14 @@
 #include <vector>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_host.h"
 
 namespace {
 
-bool hip_ok(hipError_t e) {
-  if (e == hipSuccess) return true;
-  fprintf(stderr, "nghttp2_amd_hd (sharded): HIP error %s\n", hipGetErrorString(e));
-  return false;
-}
+using hdhost::DevBuf, hdhost::round16;
 
-size_t round16(size_t x) { return (x + 15u) & ~size_t(15); }
-
-// A device buffer that grows (never shrinks) on its context's device.
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  bool reserve(size_t need) {
-    if (need <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    need = round16(need) + 256;
-    if (!hip_ok(hipMalloc(&p, need))) return false;
-    cap = need;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T *as() const { return static_cast<T *>(p); }
-};
+bool ok(hipError_t e) { return hdhost::hip_ok(e, "sharded", nullptr); }
+bool grow(DevBuf &b, size_t need) { return b.reserve(need, "sharded", nullptr, true); }  // (padded)
 
 // One shard's device context and worker thread.  The worker runs one job at
 // a time; run() hands it a job, wait() joins it.
@@ -78,7 +52,7 @@ struct Shard {
   int init_rv = 0;
 
   void loop() {
-    init_rv = hip_ok(hipSetDevice(device)) && hip_ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking))
+    init_rv = ok(hipSetDevice(device)) && ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking))
                   ? 0
                   : NGHTTP2_AMD_ERR_FATAL;
     {
@@ -158,7 +132,7 @@ void cut(const uint32_t *off, uint32_t n, uint32_t m, uint32_t *cuts) {
 template <bool DEC>
 int shard_phase1(Shard &sh, const uint8_t *src, const uint32_t *off, uint32_t s0, uint32_t s1,
                  bool want_ctx, uint64_t *total) {
-  if (!hip_ok(hipSetDevice(sh.device))) return NGHTTP2_AMD_ERR_FATAL;
+  if (!ok(hipSetDevice(sh.device))) return NGHTTP2_AMD_ERR_FATAL;
   const uint32_t n = s1 - s0;
   const uint64_t a = off[s0], b = off[s1];
   const uint64_t a16 = a & ~(uint64_t)15;
@@ -167,13 +141,13 @@ int shard_phase1(Shard &sh, const uint8_t *src, const uint32_t *off, uint32_t s0
   const size_t out_cap = DEC ? nghttp2_amd_hd_huff_decode_bound(in_bytes, n)
                              : nghttp2_amd_hd_huff_encode_bound(in_bytes, n);
   const size_t wsz = nghttp2_amd_hd_huff_workspace_size(n);
-  if (!sh.src.reserve(bytes) || !sh.src_off.reserve(4ull * (n + 1)) || !sh.dst.reserve(out_cap) ||
-      !sh.dst_off.reserve(4ull * (n + 1)) || !sh.ws.reserve(wsz) ||
-      (DEC && !sh.status.reserve(4ull * std::max(1u, n))) ||
-      (DEC && want_ctx && (!sh.fstate.reserve(2ull * std::max(1u, n)) || !sh.flags.reserve(std::max(1u, n)))))
+  if (!grow(sh.src, bytes) || !grow(sh.src_off, 4ull * (n + 1)) || !grow(sh.dst, out_cap) ||
+      !grow(sh.dst_off, 4ull * (n + 1)) || !grow(sh.ws, wsz) ||
+      (DEC && !grow(sh.status, 4ull * std::max(1u, n))) ||
+      (DEC && want_ctx && (!grow(sh.fstate, 2ull * std::max(1u, n)) || !grow(sh.flags, std::max(1u, n)))))
     return NGHTTP2_AMD_ERR_NOMEM;
-  if (!hip_ok(hipMemcpyAsync(sh.src.p, src + a16, bytes, hipMemcpyHostToDevice, sh.st)) ||
-      !hip_ok(hipMemcpyAsync(sh.src_off.p, off + s0, 4ull * (n + 1), hipMemcpyHostToDevice, sh.st)))
+  if (!ok(hipMemcpyAsync(sh.src.p, src + a16, bytes, hipMemcpyHostToDevice, sh.st)) ||
+      !ok(hipMemcpyAsync(sh.src_off.p, off + s0, 4ull * (n + 1), hipMemcpyHostToDevice, sh.st)))
     return NGHTTP2_AMD_ERR_FATAL;
   // the kernels address src + off[i]: a base moved back by the shard's first chunk
   const uint8_t *ksrc = sh.src.as<uint8_t>() - a16;
@@ -189,8 +163,8 @@ int shard_phase1(Shard &sh, const uint8_t *src, const uint32_t *off, uint32_t s0
                                           out_cap, sh.dst_off.as<uint32_t>(), sh.ws.p, sh.ws.cap, sh.st);
   if (rv != 0) return rv;
   uint32_t t = 0;
-  if (!hip_ok(hipMemcpyAsync(&t, sh.dst_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, sh.st)) ||
-      !hip_ok(hipStreamSynchronize(sh.st)))
+  if (!ok(hipMemcpyAsync(&t, sh.dst_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, sh.st)) ||
+      !ok(hipStreamSynchronize(sh.st)))
     return NGHTTP2_AMD_ERR_FATAL;
   *total = t;  // (encode: NGHTTP2_AMD_OFF_OVERFLOW when the shard overflowed)
   return 0;
@@ -201,19 +175,19 @@ int shard_phase1(Shard &sh, const uint8_t *src, const uint32_t *off, uint32_t s0
 template <bool DEC>
 int shard_phase2(Shard &sh, uint32_t s0, uint32_t s1, bool last, uint64_t base, uint64_t total,
                  uint8_t *dst, uint32_t *dst_off, int32_t *status, uint16_t *fstate, uint8_t *flags) {
-  if (!hip_ok(hipSetDevice(sh.device))) return NGHTTP2_AMD_ERR_FATAL;
+  if (!ok(hipSetDevice(sh.device))) return NGHTTP2_AMD_ERR_FATAL;
   const uint32_t n = s1 - s0;
   const uint32_t noff = last ? n + 1 : n;  // (shard k's dst_off[n] is shard k+1's dst_off[0])
-  if ((total && !hip_ok(hipMemcpyAsync(dst + base, sh.dst.p, total, hipMemcpyDeviceToHost, sh.st))) ||
-      (noff && !hip_ok(hipMemcpyAsync(dst_off + s0, sh.dst_off.p, 4ull * noff, hipMemcpyDeviceToHost, sh.st))))
+  if ((total && !ok(hipMemcpyAsync(dst + base, sh.dst.p, total, hipMemcpyDeviceToHost, sh.st))) ||
+      (noff && !ok(hipMemcpyAsync(dst_off + s0, sh.dst_off.p, 4ull * noff, hipMemcpyDeviceToHost, sh.st))))
     return NGHTTP2_AMD_ERR_FATAL;
   if (DEC && n) {
-    if (!hip_ok(hipMemcpyAsync(status + s0, sh.status.p, 4ull * n, hipMemcpyDeviceToHost, sh.st)) ||
-        (fstate && !hip_ok(hipMemcpyAsync(fstate + s0, sh.fstate.p, 2ull * n, hipMemcpyDeviceToHost, sh.st))) ||
-        (flags && !hip_ok(hipMemcpyAsync(flags + s0, sh.flags.p, n, hipMemcpyDeviceToHost, sh.st))))
+    if (!ok(hipMemcpyAsync(status + s0, sh.status.p, 4ull * n, hipMemcpyDeviceToHost, sh.st)) ||
+        (fstate && !ok(hipMemcpyAsync(fstate + s0, sh.fstate.p, 2ull * n, hipMemcpyDeviceToHost, sh.st))) ||
+        (flags && !ok(hipMemcpyAsync(flags + s0, sh.flags.p, n, hipMemcpyDeviceToHost, sh.st))))
       return NGHTTP2_AMD_ERR_FATAL;
   }
-  if (!hip_ok(hipStreamSynchronize(sh.st))) return NGHTTP2_AMD_ERR_FATAL;
+  if (!ok(hipStreamSynchronize(sh.st))) return NGHTTP2_AMD_ERR_FATAL;
   const uint32_t b32 = (uint32_t)base;
   for (uint32_t i = 0; i < noff; ++i) dst_off[s0 + i] += b32;
   return 0;
@@ -270,7 +244,7 @@ int sharded_dev(nghttp2_amd_hd_sharded *s, nghttp2_amd_hd_shard *sh) {
     nghttp2_amd_hd_shard &x = sh[k];
     Shard &c = *s->shards[k];
     x.out_bytes = 0;
-    if (!hip_ok(hipSetDevice(c.device))) {
+    if (!ok(hipSetDevice(c.device))) {
       x.rv = NGHTTP2_AMD_ERR_FATAL;
       return;
     }
@@ -279,13 +253,13 @@ int sharded_dev(nghttp2_amd_hd_sharded *s, nghttp2_amd_hd_shard *sh) {
                                                    x.dst_off, x.status, x.fstate, x.flags, c.st);
     } else {
       const size_t wsz = nghttp2_amd_hd_huff_workspace_size(x.n);
-      x.rv = c.ws.reserve(wsz) ? nghttp2_amd_hd_huff_encode_batch(x.src, x.src_off, x.n, x.dst, x.dst_cap,
+      x.rv = grow(c.ws, wsz) ? nghttp2_amd_hd_huff_encode_batch(x.src, x.src_off, x.n, x.dst, x.dst_cap,
                                                                   x.dst_off, c.ws.p, c.ws.cap, c.st)
                                : NGHTTP2_AMD_ERR_NOMEM;
     }
     uint32_t t = 0;
-    if (x.rv == 0 && (!hip_ok(hipMemcpyAsync(&t, x.dst_off + x.n, 4, hipMemcpyDeviceToHost, c.st)) ||
-                      !hip_ok(hipStreamSynchronize(c.st))))
+    if (x.rv == 0 && (!ok(hipMemcpyAsync(&t, x.dst_off + x.n, 4, hipMemcpyDeviceToHost, c.st)) ||
+                      !ok(hipStreamSynchronize(c.st))))
       x.rv = NGHTTP2_AMD_ERR_FATAL;
     x.out_bytes = t;
   });
@@ -315,7 +289,7 @@ int nghttp2_amd_hd_sharded_new(nghttp2_amd_hd_sharded **out, const int *devices,
   if (!out || !devices || ndevices == 0) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   int count = 0;
-  if (!hip_ok(hipGetDeviceCount(&count))) return NGHTTP2_AMD_ERR_FATAL;
+  if (!ok(hipGetDeviceCount(&count))) return NGHTTP2_AMD_ERR_FATAL;
   for (uint32_t k = 0; k < ndevices; ++k)
     if (devices[k] < 0 || devices[k] >= count) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   nghttp2_amd_hd_sharded *s = new (std::nothrow) nghttp2_amd_hd_sharded;

@@ -161,10 +161,15 @@ void parallel_for(size_t n, size_t grain, F &&f) {
     for (size_t i = 0; i < n; ++i) f(i);
     return;
   }
-  std::atomic<size_t> next{0};
+  // (on a cache line of its own: every fetch would else bounce the line the
+  // workers read n, grain and f's captures from, wherever the caller's frame
+  // happens to put them)
+  struct alignas(64) {
+    std::atomic<size_t> v{0};
+  } next;
   const std::function<void()> work = [&]() {
     for (;;) {
-      const size_t a = next.fetch_add(grain, std::memory_order_relaxed);
+      const size_t a = next.v.fetch_add(grain, std::memory_order_relaxed);
       if (a >= n) return;
       const size_t b = std::min(n, a + grain);
       for (size_t i = a; i < b; ++i) f(i);

@@ -76,6 +76,34 @@ def test_raw_literal_batches_match_oracle(cap):
                 [tuple(map(bytes, e)) for e in refs[c].table]
 
 
+def test_static_table_is_one_table_for_both_sides():
+    """The inflater and the deflater read one static table: for indices
+    1..61 both get_table_entry functions return the oracle's RFC 7541
+    Appendix A entry, byte for byte; index 0 and, on fresh objects with empty
+    dynamic tables, index 62 are INVALID_ARGUMENT from both."""
+    import ctypes
+    inf, de = nghttp2_amd.HpackInflater(), nghttp2_amd.HpackDeflater()
+    getters = ((inf.L.nghttp2_amd_hd_inflate_get_table_entry, inf.p),
+               (de.L.nghttp2_amd_hd_deflate_get_table_entry, de.p))
+
+    def entry(get, p, idx):
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        la, lb = ctypes.c_size_t(), ctypes.c_size_t()
+        rv = get(p, idx, ctypes.byref(a), ctypes.byref(la), ctypes.byref(b), ctypes.byref(lb))
+        if rv != 0:
+            return rv
+        return ctypes.string_at(a, la.value), la.value, ctypes.string_at(b, lb.value), lb.value
+
+    assert len(HO.STATIC) == 61
+    for idx in range(1, 62):
+        name, value = HO.STATIC[idx - 1]
+        for get, p in getters:
+            assert entry(get, p, idx) == (name, len(name), value, len(value)), idx
+    for get, p in getters:
+        assert entry(get, p, 0) == nghttp2_amd.NGHTTP2_ERR_INVALID_ARGUMENT
+        assert entry(get, p, 62) == nghttp2_amd.NGHTTP2_ERR_INVALID_ARGUMENT
+
+
 def test_same_inflater_twice_in_separate_batches():
     """The grouping stamp: an inflater's connection number from one call must
     not leak into the next (different batch, different connection order)."""
