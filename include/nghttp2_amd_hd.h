@@ -300,6 +300,55 @@ NGHTTP2_AMD_EXTERN int32_t nghttp2_amd_hd_lookup_token(const uint8_t *name, size
 NGHTTP2_AMD_EXTERN uint32_t nghttp2_amd_hd_name_hash(const uint8_t *name, size_t namelen);
 
 /* ------------------------------------------------------------------ */
+/* Header-field validation (nghttp2_check_*)                            */
+/* ------------------------------------------------------------------ */
+/*
+ * Replaces the per-byte table scans nghttp2_http_on_header
+ * (lib/nghttp2_http.c:405-447) runs on every name and value the inflater
+ * hands over: nghttp2_check_header_name, _header_value,
+ * _header_value_rfc9113, _method, _path, _authority (nghttp2.h) and the
+ * internal nghttp2_check_nonempty_header_name (lib/nghttp2_helper.h), all in
+ * lib/nghttp2_helper.c:346-558.  One pass over a string answers all of them:
+ * the result is a uint8 mask, a bit set exactly when the reference function
+ * returns 1 for the string.
+ *
+ * Out of scope: nghttp2_check_nonempty_header_name's 0-versus-2 result for a
+ * refused name (it depends on which bad byte comes first; NAME_LOWER only
+ * says whether it returns 1), and the authority table without '@' that is
+ * private to lib/nghttp2_http.c (AUTHORITY is the public
+ * nghttp2_check_authority, which allows '@').
+ */
+#define NGHTTP2_AMD_CHECK_NAME 0x01u          /* nghttp2_check_header_name: empty 0, a leading ':' skipped, ":" 0 */
+#define NGHTTP2_AMD_CHECK_VALUE 0x02u         /* nghttp2_check_header_value: empty 1 */
+#define NGHTTP2_AMD_CHECK_VALUE_RFC9113 0x04u /* nghttp2_check_header_value_rfc9113: and no SP / HT at either end */
+#define NGHTTP2_AMD_CHECK_METHOD 0x08u        /* nghttp2_check_method: empty 0 */
+#define NGHTTP2_AMD_CHECK_PATH 0x10u          /* nghttp2_check_path: empty 1 */
+#define NGHTTP2_AMD_CHECK_AUTHORITY 0x20u     /* nghttp2_check_authority: empty 1 */
+#define NGHTTP2_AMD_CHECK_NAME_LOWER 0x40u    /* nghttp2_check_nonempty_header_name(...) == 1: no ':' exemption, empty 1 */
+#define NGHTTP2_AMD_CHECK_INVALID 0x80u       /* the string was not examined; every other bit is 0 */
+
+/* The mask of one host string (no GPU). */
+NGHTTP2_AMD_EXTERN uint8_t nghttp2_amd_hd_check_field(const uint8_t *s, size_t len);
+
+/*
+ * The masks of N strings: mask[i] (OUT, n bytes) for string i of the pool
+ * (batch layout: 16-byte aligned, readable to align_up(off[n], 16) + 16).
+ * len == NULL: string i = pool[off[i] .. off[i+1]).  len given: string i =
+ * pool[off[i] .. off[i] + len[i]) -- what nghttp2_amd_hd_huff_decode_batch_auto
+ * leaves behind as (dst, dst_off, status), dense per task with unspecified
+ * bytes between tasks, so a decode's output is validated in the same stream
+ * with no host round trip and no repacking.  off (n + 1 entries) must be
+ * non-decreasing.  A string gets NGHTTP2_AMD_CHECK_INVALID, and none of its
+ * bytes is read, when len[i] < 0 (a failed decode's status), off[i] + len[i]
+ * > off[i+1], or off[i] > off[i+1].  Bytes outside a string never influence
+ * its mask.  Device pointers, asynchronous on `stream`; n == 0 returns 0, a
+ * NULL pool, off or mask NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_check_fields_batch(const uint8_t *pool, const uint32_t *off,
+                                                         const int32_t *len, uint32_t n, uint8_t *mask,
+                                                         void *stream);
+
+/* ------------------------------------------------------------------ */
 /* Batched HPACK inflate front-end               */
 /* ------------------------------------------------------------------ */
 /*
@@ -364,6 +413,26 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks(nghttp2_amd_hd_inflater *co
                                   size_t nva_cap, size_t *nva_used, uint8_t *arena,
                                   size_t arena_cap, size_t *arena_used, int32_t *block_status,
                                   void *stream);
+
+/*
+ * nghttp2_amd_hd_inflate_blocks that also validates what it emits:
+ * nv_checks[2 k] is the NGHTTP2_AMD_CHECK_* mask of field k's name,
+ * nv_checks[2 k + 1] that of its value (2 * nva_cap bytes; the first
+ * 2 * *nva_used are written, for a block that ends in
+ * NGHTTP2_AMD_ERR_HEADER_COMP those of the fields emitted before the error).
+ * Huffman literals are checked on the GPU right behind their decode
+ * (nghttp2_amd_hd_check_fields_batch on the decode's output, one more launch
+ * and one byte per literal more in the copy back), raw literals on the host
+ * inside the replay, static-table entries once per process, dynamic-table
+ * entries when they are inserted: an indexed field costs no byte scan.
+ * nv_checks == NULL is nghttp2_amd_hd_inflate_blocks itself.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_inflater *const *inflaters,
+                                  uint32_t nblocks, const uint8_t *const *blocks,
+                                  const size_t *block_lens, nghttp2_amd_hd_nv *nva,
+                                  size_t nva_cap, size_t *nva_used, uint8_t *arena,
+                                  size_t arena_cap, size_t *arena_used, int32_t *block_status,
+                                  uint8_t *nv_checks, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* Batched HPACK deflate front-end                                      */

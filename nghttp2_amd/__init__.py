@@ -8,6 +8,14 @@ plumbing.  There is no CPU fallback: every compute call goes to the HIP
 library and raises if it is missing.
 """
 from .hd import (  # noqa: F401
+    CHECK_AUTHORITY,
+    CHECK_INVALID,
+    CHECK_METHOD,
+    CHECK_NAME,
+    CHECK_NAME_LOWER,
+    CHECK_PATH,
+    CHECK_VALUE,
+    CHECK_VALUE_RFC9113,
     HpackDeflater,
     HpackInflater,
     HuffmanBatchCodec,
@@ -15,6 +23,7 @@ from .hd import (  # noqa: F401
     NGHTTP2_ERR_HEADER_COMP,
     NGHTTP2_ERR_INSUFF_BUFSIZE,
     NGHTTP2_ERR_INVALID_ARGUMENT,
+    check_field,
     decode_length,
     lib,
     lib_path,

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_field_classes.h"
 #include "hd_host.h"
 #include "host_threads.h"
 
@@ -45,10 +46,16 @@ const uint32_t kDefaultTable = 4096;   // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
 // Insertion and eviction allocate nothing once the rings have grown to the
 // connection's working size; a ring that cannot place an entry is compacted
 // into one twice as large.
+// An entry also carries the NGHTTP2_AMD_CHECK_* masks of its name and value
+// (kUnchecked until a checked call computes them: at insertion, or at the
+// first reference to an entry that an unchecked call inserted), so an indexed
+// field costs a checked call no byte scan.
+const uint8_t kUnchecked = NGHTTP2_AMD_CHECK_INVALID;
 struct DynTable {
   struct Ent {
     size_t off;
     uint32_t nl, vl;
+    uint8_t cn = kUnchecked, cv = kUnchecked;
   };
   std::vector<Ent> ents;   // ring, capacity a power of two
   size_t e_first = 0;      // oldest entry
@@ -58,6 +65,7 @@ struct DynTable {
   const Ent &newest(size_t k) const {  // k = 0: the most recent (dynamic index 62)
     return ents[(e_first + count - 1 - k) & (ents.size() - 1)];
   }
+  Ent &newest(size_t k) { return ents[(e_first + count - 1 - k) & (ents.size() - 1)]; }
   const uint8_t *name(const Ent &e) const { return buf.data() + e.off; }
   const uint8_t *value(const Ent &e) const { return buf.data() + e.off + e.nl; }
   size_t bytes(const Ent &e) const { return (size_t)e.nl + e.vl; }
@@ -94,7 +102,7 @@ struct DynTable {
     buf.swap(nb);
   }
   // n / v must not point into this table (the caller passes copies)
-  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl) {
+  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv) {
     if (count == ents.size()) {  // grow the descriptor ring, oldest first
       std::vector<Ent> ne(ents.empty() ? 16 : 2 * ents.size());
       for (size_t k = 0; k < count; ++k) ne[k] = ents[(e_first + k) & (ents.size() - 1)];
@@ -108,7 +116,7 @@ struct DynTable {
     }
     if (nl) memcpy(buf.data() + at, n, nl);
     if (vl) memcpy(buf.data() + at + nl, v, vl);
-    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl};
+    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, cn, cv};
     ++count;
   }
 };
@@ -138,11 +146,12 @@ struct nghttp2_amd_hd_inflater {
   // insert it unless it is larger than the whole table.  n / v are copies
   // outside the table (the caller's emitted field), so a name taken from an
   // entry that this insertion evicts stays valid, as in the reference.
-  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl) {
+  // cn / cv: the field's check masks (kUnchecked from an unchecked call).
+  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv) {
     const size_t room = nl + vl + kEntryOverhead;
     while (bufsize + room > bufsize_max && table.count) evict_oldest();
     if (room > bufsize_max) return;
-    table.push(n, nl, v, vl);
+    table.push(n, nl, v, vl, cn, cv);
     bufsize += room;
     max_nl = std::max(max_nl, nl);
     max_vl = std::max(max_vl, vl);
@@ -157,6 +166,30 @@ struct nghttp2_amd_hd_inflater {
     *nl = e.nl;
     *v = (const char *)table.value(e);
     *vl = e.vl;
+  }
+  // the check masks of entry idx (as entry()): the static table's are computed
+  // once per process, a dynamic entry's are in its descriptor
+  void entry_checks(size_t idx, uint8_t *cn, uint8_t *cv) {
+    if (idx < kStaticLen) {
+      struct Masks {
+        uint8_t m[kStaticLen][2];
+      };
+      static const Masks st = [] {
+        Masks t;
+        for (uint32_t i = 0; i < kStaticLen; ++i)
+          for (int w = 0; w < 2; ++w)
+            t.m[i][w] = hdcls::check_field((const uint8_t *)kStatic[i][w], kStaticLens.len[i][w]);
+        return t;
+      }();
+      *cn = st.m[idx][0];
+      *cv = st.m[idx][1];
+      return;
+    }
+    DynTable::Ent &e = table.newest(idx - kStaticLen);
+    if (e.cn == kUnchecked) e.cn = hdcls::check_field(table.name(e), e.nl);
+    if (e.cv == kUnchecked) e.cv = hdcls::check_field(table.value(e), e.vl);
+    *cn = e.cn;
+    *cv = e.cv;
   }
 };
 
@@ -205,6 +238,7 @@ struct alignas(128) Block {  // (aligned as BlockOut)
 struct Rec {
   uint32_t name_off, name_len, value_off, value_len;
   uint8_t flags;
+  uint8_t cn, cv;  // the check masks of name and value (a checked call)
 };
 // A growable byte buffer written through a raw pointer (no per-append
 // capacity check or zero fill): a block's name\0value\0 runs.
@@ -308,6 +342,7 @@ struct LitSrc {
   const uint8_t *dec;
   const uint32_t *slot;
   const int32_t *st;
+  const uint8_t *chk;  // a checked call: the decoded literals' check masks (the GPU's)
   // false: -523 (bad padding or EOS, hd_inflate_read_huff :1740-1750)
   bool get(const Lit &l, const char **p, size_t *n) const {
     if (l.huff < 0) {
@@ -321,6 +356,9 @@ struct LitSrc {
     *n = (size_t)s;
     return true;
   }
+  // the check mask of a literal get() returned: a raw one is scanned here (on
+  // the replay's thread), a Huffman one was scanned behind its decode
+  uint8_t check(const Lit &l) const { return l.huff < 0 ? hdcls::check_field(l.p, l.len) : chk[l.huff]; }
 };
 
 // What one dynamic-table reference of block b can emit (name + value): any
@@ -358,9 +396,11 @@ struct BlockSink {
     out.recs.clear();
     out.bytes.clear();
   }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags) {
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv) {
     Rec r;
     r.flags = flags;
+    r.cn = cn;
+    r.cv = cv;
     r.name_off = (uint32_t)out.bytes.size();
     r.name_len = (uint32_t)nl;
     r.value_off = r.name_off + (uint32_t)nl + 1u;
@@ -382,10 +422,15 @@ struct DirectSink {
   uint8_t *arena;
   nghttp2_amd_hd_nv *nva;
   int32_t *status;
+  uint8_t *checks;  // the caller's nv_checks, or nullptr
   size_t ar = 0, nv = 0, nv0 = 0;
   uint32_t block = 0;
   void begin() { nv0 = nv; }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags) {
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv) {
+    if (checks) {
+      checks[2 * nv] = cn;
+      checks[2 * nv + 1] = cv;
+    }
     nghttp2_amd_hd_nv &d = nva[nv++];
     d.block = block;
     d.flags = flags;
@@ -406,8 +451,9 @@ struct DirectSink {
   int32_t count() const { return (int32_t)(nv - nv0); }
 };
 
+// chk: a checked call -- every emitted name and value with its check mask.
 template <class Sink>
-void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, Sink &out) {
+void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, bool chk, Sink &out) {
   out.begin();
   bool ok = !inf->bad;
   bool head = true;  // size updates only at the head of a block
@@ -431,13 +477,15 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     head = false;
     const char *n, *v;
     size_t nl, vl;
+    uint8_t cn = kUnchecked, cv = kUnchecked;
     if (op.kind == Op::INDEXED) {  // hd_inflate_commit_indexed
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
         break;
       }
       inf->entry(op.value - 1, &n, &nl, &v, &vl);
-      out.emit(n, nl, v, vl, 0);
+      if (chk) inf->entry_checks(op.value - 1, &cn, &cv);
+      out.emit(n, nl, v, vl, 0, cn, cv);
       continue;
     }
     if (op.new_name) {  // hd_inflate_commit_newname
@@ -445,6 +493,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
         ok = false;
         break;
       }
+      if (chk) cn = ls.check(op.name);
     } else {  // hd_inflate_commit_indname
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
@@ -453,15 +502,18 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       const char *v0;
       size_t vl0;
       inf->entry(op.value - 1, &n, &nl, &v0, &vl0);
+      uint8_t cv0;
+      if (chk) inf->entry_checks(op.value - 1, &cn, &cv0);
     }
     if (!ls.get(op.val, &v, &vl)) {
       ok = false;
       break;
     }
+    if (chk) cv = ls.check(op.val);
     const uint8_t flags = op.no_index ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
-    out.emit(n, nl, v, vl, flags);
+    out.emit(n, nl, v, vl, flags, cn, cv);
     if (op.index_required)  // the table copies the field just emitted
-      inf->add(out.last_name(), nl, out.last_value(), vl);
+      inf->add(out.last_name(), nl, out.last_value(), vl, cn, cv);
   }
   // truncated or malformed wire after the parsed representations; and a
   // block that ends while a table size update is still expected
@@ -486,6 +538,7 @@ struct Dest {
   uint8_t *arena;
   size_t arena_cap, *arena_used;
   int32_t *block_status;
+  uint8_t *nv_checks;  // a checked call: two masks per field; else nullptr
 };
 
 // The parts of a parsed block's output bound: a field per representation,
@@ -601,7 +654,10 @@ int zc_mode() {
 // in one decode, queued on the caller's stream.  The pinned pools are sized
 // first, so number_and_copy can fill the input pool in place.  *ls says where
 // replay finds the decoded literals once the stream has been waited for.
-int stage_decode(Engine &E, uint32_t nblocks, void *stream, Phases &ph, LitSrc *ls) {
+// A checked call queues nghttp2_amd_hd_check_fields_batch over the decode's
+// (dst, slots, status) right behind it; the masks, a byte per literal, sit
+// behind the status words and come back with them in the same copy.
+int stage_decode(Engine &E, uint32_t nblocks, bool checks, void *stream, Phases &ph, LitSrc *ls) {
   for (uint32_t i = 0; i < nblocks; ++i) {
     E.nhuff[i + 1] += E.nhuff[i];
     E.hbytes[i + 1] += E.hbytes[i];
@@ -617,19 +673,22 @@ int stage_decode(Engine &E, uint32_t nblocks, void *stream, Phases &ph, LitSrc *
   const bool zero_copy = mode == 1;
   const size_t in_bytes = ((size_t)hb + 15u) / 16u * 16u + 16u;
   const size_t out_bytes = nh ? nghttp2_amd_hd_huff_decode_bound(hb, nh) : 0;
-  const size_t slots = (size_t)nh + 1u, meta = 3u * slots * sizeof(uint32_t);
+  // (the check reads whole 16-byte chunks up to the last slot's end, and one
+  // at it when every literal is empty)
+  const size_t out_alloc = out_bytes + (checks ? 16u : 0u);
+  const size_t slots = (size_t)nh + 1u, meta = 3u * slots * sizeof(uint32_t) + (checks ? nh : 0u);
   // (the output pool is a D2H copy target unless the kernel writes it
   // through the mapping, mode 1; the input pools are mapped unless mode 0;
   // mode 2 needs no device copy of the input)
-  if (nh && (!E.h_pool.reserve(in_bytes, kLayer, mode != 0) || !E.h_out.reserve(out_bytes, kLayer, zero_copy) ||
+  if (nh && (!E.h_pool.reserve(in_bytes, kLayer, mode != 0) || !E.h_out.reserve(out_alloc, kLayer, zero_copy) ||
              !E.h_meta.reserve(meta, kLayer, mode != 0) ||
              (!zero_copy && ((mode == 0 && !E.d_in.reserve(in_bytes, kLayer)) ||
-                             !E.d_out.reserve(out_bytes, kLayer) || !E.d_meta.reserve(meta, kLayer)))))
+                             !E.d_out.reserve(out_alloc, kLayer) || !E.d_meta.reserve(meta, kLayer)))))
     return NGHTTP2_AMD_ERR_NOMEM;
   ph.mark("pools");
   number_and_copy(E, nblocks);
   ph.mark("number+copy");
-  *ls = LitSrc{nullptr, nullptr, nullptr};
+  *ls = LitSrc{nullptr, nullptr, nullptr, nullptr};
   if (!nh) return 0;
   hipStream_t st = (hipStream_t)stream;
   uint32_t *const h_meta = E.h_meta.as<uint32_t>();
@@ -661,14 +720,19 @@ int stage_decode(Engine &E, uint32_t nblocks, void *stream, Phases &ph, LitSrc *
   const int rv = nghttp2_amd_hd_huff_decode_batch_auto(src, src_off, nh, hb, dst, out_bytes, d_slot, d_st,
                                                        nullptr, nullptr, stream);
   if (rv) return drain(rv);
+  if (checks) {
+    const int rc = nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, (uint8_t *)(d_st + nh), stream);
+    if (rc) return drain(rc);
+  }
   uint32_t *h_slot = h_meta + slots;
   int32_t *h_st = (int32_t *)(h_slot + slots);
   if (!zero_copy &&
       (hipMemcpyAsync(E.h_out.p, dst, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
        hipMemcpyAsync(h_slot, d_slot, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess))
+       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t) + (checks ? nh : 0u), hipMemcpyDeviceToHost, st) !=
+           hipSuccess))
     return drain(NGHTTP2_AMD_ERR_FATAL);
-  *ls = LitSrc{E.h_out.as<uint8_t>(), h_slot, h_st};
+  *ls = LitSrc{E.h_out.as<uint8_t>(), h_slot, h_st, checks ? (const uint8_t *)(h_st + nh) : nullptr};
   return 0;
 }
 
@@ -720,12 +784,16 @@ bool may_cut(const Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
 
 // One replayed block's fields into the caller's field array at nv_base and arena at ar_base.
 void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_base, nghttp2_amd_hd_nv *nva,
-                 uint8_t *arena) {
+                 uint8_t *arena, uint8_t *checks) {
   const uint32_t ab = (uint32_t)ar_base;
   if (!o.bytes.empty()) memcpy(arena + ab, o.bytes.data(), o.bytes.size());
   nghttp2_amd_hd_nv *d = nva + nv_base;
   for (const Rec &r : o.recs)
     *d++ = nghttp2_amd_hd_nv{block, ab + r.name_off, r.name_len, ab + r.value_off, r.value_len, r.flags};
+  if (checks) {
+    uint8_t *c = checks + 2 * nv_base;
+    for (const Rec &r : o.recs) *c++ = r.cn, *c++ = r.cv;
+  }
 }
 
 // "replay direct" -- pass 2 for a batch of one connection (a serial replay
@@ -738,7 +806,8 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
   if (ls.st && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
   ph.mark("gpu wait");
   nghttp2_amd_hd_inflater *c = E.conns[0];
-  DirectSink ds{d.arena, d.nva, d.block_status};
+  DirectSink ds{d.arena, d.nva, d.block_status, d.nv_checks};
+  const bool chk = d.nv_checks != nullptr;
   uint32_t cut = nblocks;
   for (uint32_t i = 0; i < nblocks; ++i) {
     const Block &b = E.bl[i];
@@ -747,19 +816,19 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
     const uint64_t ar_b = block_ar_bound(b, dyn_ref_bound(c, b.lit_name, b.lit_val));
     ds.block = i;
     if (ds.nv + b.nv <= d.nva_cap && ar_b <= d.arena_cap - ds.ar) {
-      replay_block(c, b, ls, ds);
+      replay_block(c, b, ls, chk, ds);
       continue;
     }
     nghttp2_amd_hd_inflater keep = *c;
     BlockOut scratch;
     BlockSink bs{scratch};
-    replay_block(c, b, ls, bs);
+    replay_block(c, b, ls, chk, bs);
     if (ds.nv + scratch.recs.size() > d.nva_cap || scratch.bytes.size() > d.arena_cap - ds.ar) {
       *c = std::move(keep);
       cut = i;
       break;
     }
-    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena);
+    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena, d.nv_checks);
     ds.nv += scratch.recs.size();
     ds.ar += scratch.bytes.size();
     d.block_status[i] = scratch.status;
@@ -790,10 +859,11 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
   // replay allocates only while they grow
   std::vector<BlockOut> &outs = E.outs;
   if (outs.size() < nblocks) outs.resize(nblocks);
+  const bool chk = d.nv_checks != nullptr;
   parallel_for(conns.size(), 1, [&](size_t c) {
     for (uint32_t j = E.cstart[c]; j < E.cstart[c + 1]; ++j) {
       BlockSink bs{outs[E.corder[j]]};
-      replay_block(conns[c], E.bl[E.corder[j]], ls, bs);
+      replay_block(conns[c], E.bl[E.corder[j]], ls, chk, bs);
     }
   });
   ph.mark("replay");
@@ -821,11 +891,11 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
     for (size_t c = 0; c < conns.size(); ++c) *conns[c] = std::move(snap[c]);
     BlockOut scratch;
     BlockSink ss{scratch};
-    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], E.bl[i], ls, ss);
+    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], E.bl[i], ls, chk, ss);
     for (uint32_t j = cut; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
   }
   parallel_for(cut, 256, [&](size_t i) {
-    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena);
+    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena, d.nv_checks);
     d.block_status[i] = outs[i].status;
   });
   ph.mark("place");
@@ -934,6 +1004,15 @@ int nghttp2_amd_hd_inflate_blocks(nghttp2_amd_hd_inflater *const *inflaters, uin
                                   nghttp2_amd_hd_nv *nva, size_t nva_cap, size_t *nva_used,
                                   uint8_t *arena, size_t arena_cap, size_t *arena_used,
                                   int32_t *block_status, void *stream) {
+  return nghttp2_amd_hd_inflate_blocks_checked(inflaters, nblocks, blocks, block_lens, nva, nva_cap, nva_used,
+                                               arena, arena_cap, arena_used, block_status, nullptr, stream);
+}
+
+int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks,
+                                          const uint8_t *const *blocks, const size_t *block_lens,
+                                          nghttp2_amd_hd_nv *nva, size_t nva_cap, size_t *nva_used,
+                                          uint8_t *arena, size_t arena_cap, size_t *arena_used,
+                                          int32_t *block_status, uint8_t *nv_checks, void *stream) {
   if (nva_used) *nva_used = 0;
   if (arena_used) *arena_used = 0;
   if (nblocks == 0) return 0;
@@ -946,11 +1025,11 @@ int nghttp2_amd_hd_inflate_blocks(nghttp2_amd_hd_inflater *const *inflaters, uin
   Phases ph("inflate");
   std::lock_guard<std::mutex> guard(engine().mu);
   Engine &E = engine();
-  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status};
+  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status, nv_checks};
   parse_blocks(E, nblocks, blocks, block_lens);
   ph.mark("parse blocks");
   LitSrc ls;
-  if (const int rv = stage_decode(E, nblocks, stream, ph, &ls)) return rv;
+  if (const int rv = stage_decode(E, nblocks, nv_checks != nullptr, stream, ph, &ls)) return rv;
   ph.mark("gpu issued");
   // (the decode runs while the host groups the blocks by connection and
   // bounds the output; replay waits for it)

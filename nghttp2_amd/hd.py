@@ -33,6 +33,17 @@ NGHTTP2_ERR_HEADER_COMP = -523
 NGHTTP2_ERR_INSUFF_BUFSIZE = -525
 NGHTTP2_ERR_FATAL = -900
 
+# check_field / check_fields / inflate_blocks(checks=True): a bit is set
+# exactly when the reference's nghttp2_check_* function returns 1
+CHECK_NAME = 0x01             # nghttp2_check_header_name
+CHECK_VALUE = 0x02            # nghttp2_check_header_value
+CHECK_VALUE_RFC9113 = 0x04    # nghttp2_check_header_value_rfc9113
+CHECK_METHOD = 0x08           # nghttp2_check_method
+CHECK_PATH = 0x10             # nghttp2_check_path
+CHECK_AUTHORITY = 0x20        # nghttp2_check_authority
+CHECK_NAME_LOWER = 0x40       # nghttp2_check_nonempty_header_name(...) == 1
+CHECK_INVALID = 0x80          # the string was not examined
+
 _lib = None
 
 
@@ -86,6 +97,9 @@ def lib():
         L.nghttp2_amd_hd_lookup_token.restype = ctypes.c_int32
         L.nghttp2_amd_hd_name_hash.argtypes = [ctypes.c_char_p, sz]
         L.nghttp2_amd_hd_name_hash.restype = ctypes.c_uint32
+        L.nghttp2_amd_hd_check_field.argtypes = [ctypes.c_char_p, sz]
+        L.nghttp2_amd_hd_check_field.restype = ctypes.c_uint8
+        L.nghttp2_amd_hd_check_fields_batch.argtypes = [vp, vp, vp, u32, vp, vp]
         _lib = L
     return _lib
 
@@ -100,6 +114,13 @@ def name_hash(name):
     """Host FNV-1a name hash (lib/nghttp2_hd.c:536-547)."""
     name = bytes(name)
     return lib().nghttp2_amd_hd_name_hash(name, len(name))
+
+
+def check_field(s):
+    """Host nghttp2_check_* of one string (lib/nghttp2_helper.c:346-558): the
+    CHECK_* mask."""
+    s = bytes(s)
+    return lib().nghttp2_amd_hd_check_field(s, len(s))
 
 
 def tables_ref_layout():
@@ -224,6 +245,20 @@ class HuffmanBatchCodec:
             _p(names), _p(name_off), n, _p(token), _p(hash), _stream(stream))
         _check(rv, "name_tokens_batch")
         return token[:n], hash[:n]
+
+    def check_fields(self, pool, off, len=None, mask=None, stream=None):
+        """nghttp2_check_* (lib/nghttp2_helper.c:346-558) for every string of
+        the batch: returns mask uint8[n] of CHECK_* bits.  String i is
+        pool[off[i]:off[i+1]], or with len (int32[n], e.g. decode_auto's
+        status next to its dst and dst_off) pool[off[i]:off[i]+len[i]]; a
+        string with a negative or overrunning len gets CHECK_INVALID."""
+        n = off.numel() - 1
+        if mask is None:
+            mask = self._empty(max(1, n), self.torch.uint8, stream)
+        rv = self.L.nghttp2_amd_hd_check_fields_batch(
+            _p(pool), _p(off), _p(len), n, _p(mask), _stream(stream))
+        _check(rv, "check_fields_batch")
+        return mask[:n]
 
     def emit_strings(self, src, src_off, raw_bytes=None, dst=None, dst_off=None, stream=None):
         """HPACK string literals (emit_string, lib/nghttp2_hd.c:1001-1044) for
@@ -371,6 +406,9 @@ def _inflate_lib():
         L.nghttp2_amd_hd_inflate_blocks.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, sz,
                                                     ctypes.POINTER(sz), vp, sz,
                                                     ctypes.POINTER(sz), vp, vp]
+        L.nghttp2_amd_hd_inflate_blocks_checked.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, sz,
+                                                            ctypes.POINTER(sz), vp, sz,
+                                                            ctypes.POINTER(sz), vp, vp, vp]
         L._inflate_bound = True
     return L
 
@@ -425,13 +463,17 @@ _NV_DTYPE = np.dtype([("block", "<u4"), ("name_off", "<u4"), ("name_len", "<u4")
 assert _NV_DTYPE.itemsize == ctypes.sizeof(_Nv)
 
 
-def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None, retry=True):
+def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None, retry=True,
+                   checks=False):
     """Inflate complete header blocks, block i against inflaters[i], with
     every Huffman literal decoded in one GPU batch.  Returns
     (status[i], fields[i] = [(name, value, flags)]).  A batch that outgrows
     the field/arena buffers is cut at the first block that does not fit
     (status NGHTTP2_ERR_BUFFER_ERROR from there on, those blocks not
     applied); with retry the rest is resubmitted with buffers twice the size.
+    With checks the call is nghttp2_amd_hd_inflate_blocks_checked and a third
+    result follows: a uint8 array (nfields, 2) of the CHECK_* masks of every
+    emitted field's name and value, in the order of the fields.
     The blocks go in as one joined buffer and the fields come out of
     uninitialised numpy buffers (no per-block ctypes objects, no zero fill)."""
     L = _inflate_lib()
@@ -459,6 +501,7 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
             s = None
     status = [NGHTTP2_ERR_BUFFER_ERROR] * nb
     fields = [[] for _ in range(nb)]
+    masks = []
     first = 0
     vp = ctypes.c_void_p
     while first < nb:
@@ -470,14 +513,23 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
         arena = np.empty(max(1, arena_cap), dtype=np.uint8)
         st = np.empty(m, dtype=np.int32)
         nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
-        rv = L.nghttp2_amd_hd_inflate_blocks(vp(infs.ctypes.data), m, vp(ptrs.ctypes.data),
-                                             vp(lens.ctypes.data), vp(nva.ctypes.data), nva_cap,
-                                             ctypes.byref(nv_used), vp(arena.ctypes.data), arena_cap,
-                                             ctypes.byref(ar_used), vp(st.ctypes.data), s)
+        if checks:
+            chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8)
+            rv = L.nghttp2_amd_hd_inflate_blocks_checked(
+                vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
+                vp(nva.ctypes.data), nva_cap, ctypes.byref(nv_used), vp(arena.ctypes.data),
+                arena_cap, ctypes.byref(ar_used), vp(st.ctypes.data), vp(chk.ctypes.data), s)
+        else:
+            rv = L.nghttp2_amd_hd_inflate_blocks(vp(infs.ctypes.data), m, vp(ptrs.ctypes.data),
+                                                 vp(lens.ctypes.data), vp(nva.ctypes.data), nva_cap,
+                                                 ctypes.byref(nv_used), vp(arena.ctypes.data), arena_cap,
+                                                 ctypes.byref(ar_used), vp(st.ctypes.data), s)
         if rv != NGHTTP2_ERR_BUFFER_ERROR:
             _check(rv, "inflate_blocks")
         raw = arena[:ar_used.value].tobytes()
         nv = nva[:nv_used.value]
+        if checks:
+            masks.append(chk[:nv_used.value].copy())
         for b, no, nl, vo, vl, fl in zip((nv["block"] + first).tolist(), nv["name_off"].tolist(),
                                          nv["name_len"].tolist(), nv["value_off"].tolist(),
                                          nv["value_len"].tolist(), nv["flags"].tolist()):
@@ -493,6 +545,8 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
                 break
             if done == 0:
                 nva_cap, arena_cap = 2 * nva_cap + 16, 2 * arena_cap + 4096
+    if checks:
+        return status, fields, (np.concatenate(masks) if masks else np.zeros((0, 2), np.uint8))
     return status, fields
 
 

@@ -12,6 +12,14 @@
            (lib/nghttp2_hd.c:137, :536) over 1M header names, device-resident;
            algorithmic bytes sum(L) + 12 N (name bytes + offset in, token +
            hash out) over the kernel time (HIP events on its stream).
+  check    nghttp2_amd_hd_check_fields_batch: nghttp2_check_* masks of 1M
+           mixed values and of the config-2 pseudo-headers, device-resident,
+           alternated with the encode count (k_enc_count<false>: the same
+           bytes, one LDS lookup per byte) on the same pools; best of the
+           steps by HIP events, GB/s of R + 5 N bytes.
+  inflate_checked  nghttp2_amd_hd_inflate_blocks_checked against
+           nghttp2_amd_hd_inflate_blocks on the 2,048-block batch, alternated:
+           what the check launch and the mask bytes in the copy back cost.
 
 Prints one JSON object.  Not the bench.py contract (that is the hot path
 itself); the numbers go to DESIGN.md."""
@@ -107,6 +115,106 @@ def bench_names(steps=50, long_frac=0.02):
     return {"names": n, "name_bytes": raw, "us_per_batch": round(t * 1e6, 2),
             "GBps_algorithmic": round(B / t / 1e9, 1), "hbm_frac": round(B / t / 8.0e12, 4),
             "Gnames_per_s": round(n / t / 1e9, 3), "long_wave_frac": long_frac}
+
+
+def bench_check(steps=30):
+    """check_fields against encode_count, alternated call by call on the same
+    device-resident pool in one process; each call between two HIP events,
+    the best of the steps of each."""
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import workloads as W
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import field_checks_ref as R
+    dev = torch.device("cuda:0")
+    codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    n = 1 << 20
+    out = {}
+    for label, (pool, off) in (("mixed_1M", W.gen_mixed_range(W.mixed_lengths(n), 0, n, threads=8)),
+                               ("pseudo_1M", W.gen_pseudo_headers(n))):
+        raw = int(off[-1])
+        src = torch.from_numpy(pool).to(dev)
+        so = torch.from_numpy(off.view(np.int32)).to(dev)
+        mask = codec.check_fields(src, so)
+        cnt = codec.encode_count(src, so)
+        torch.cuda.synchronize()
+        k = 5000  # parity on a sample
+        got = mask[:k].cpu().numpy()
+        assert all(int(got[i]) == R.mask(pool[off[i]:off[i + 1]].tobytes()) for i in range(k))
+        s = torch.cuda.current_stream()
+        for _ in range(5):
+            codec.check_fields(src, so, mask=mask)
+            codec.encode_count(src, so, enc_len=cnt)
+        ev = []
+        for _ in range(steps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record(s)
+            codec.check_fields(src, so, mask=mask)
+            e[1].record(s)
+            e[2].record(s)
+            codec.encode_count(src, so, enc_len=cnt)
+            e[3].record(s)
+            ev.append(e)
+        torch.cuda.synchronize()
+        tc = min(e[0].elapsed_time(e[1]) for e in ev) * 1e-3
+        te = min(e[2].elapsed_time(e[3]) for e in ev) * 1e-3
+        B = raw + 5 * n
+        out[label] = {"strings": n, "raw_bytes": raw, "check_us": round(tc * 1e6, 2),
+                      "encode_count_us": round(te * 1e6, 2), "check_over_count": round(tc / te, 3),
+                      "check_GBps_R_plus_5N": round(B / tc / 1e9, 1),
+                      "count_GBps_R_plus_5N": round(B / te / 1e9, 1),
+                      "check_us_median": round(float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e3, 2),
+                      "encode_count_us_median": round(float(np.median([e[2].elapsed_time(e[3]) for e in ev])) * 1e3, 2)}
+    return out
+
+
+def bench_inflate_checked(nconn=256, per_conn=8, fields=16, alternations=15):
+    """The C call of the 2,048-block inflate row with and without nv_checks,
+    alternated call by call (no indexing: every call sees the same tables);
+    best and median of each, and the difference."""
+    import ctypes
+    import statistics
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    blocks, conns = make_blocks(nconn, per_conn, fields)
+    wire = sum(len(b) for b in blocks)
+    L = hd._inflate_lib()
+    m = len(blocks)
+    keep = [ctypes.create_string_buffer(b, len(b)) for b in blocks]
+    ptrs = (ctypes.c_void_p * m)(*[ctypes.cast(k, ctypes.c_void_p) for k in keep])
+    lens = (ctypes.c_size_t * m)(*[len(b) for b in blocks])
+    nva_cap, arena_cap = wire + 16, 8 * wire + 4096
+    nva = (hd._Nv * nva_cap)()
+    arena = (ctypes.c_uint8 * arena_cap)()
+    chk = (ctypes.c_uint8 * (2 * nva_cap))()
+    stc = (ctypes.c_int32 * m)()
+    nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
+    import torch
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+    ip = (ctypes.c_void_p * m)(*[infs[c].p.value for c in conns])
+
+    def call(checked):
+        t0 = time.perf_counter()
+        rv = L.nghttp2_amd_hd_inflate_blocks_checked(ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used),
+                                                     arena, arena_cap, ctypes.byref(ar_used), stc,
+                                                     chk if checked else None, s)
+        t = time.perf_counter() - t0
+        assert rv == 0
+        return t
+    for _ in range(3):
+        call(True), call(False)
+    tp, tc = [], []
+    for _ in range(alternations):
+        tp.append(call(False))
+        tc.append(call(True))
+    nf = nv_used.value
+    return {"blocks": m, "connections": nconn, "fields": nf, "wire_bytes": wire, "alternations": alternations,
+            "plain_s_best": round(min(tp), 6), "checked_s_best": round(min(tc), 6),
+            "plain_s_median": round(statistics.median(tp), 6), "checked_s_median": round(statistics.median(tc), 6),
+            "extra_us_best": round((min(tc) - min(tp)) * 1e6, 1),
+            "extra_us_median": round((statistics.median(tc) - statistics.median(tp)) * 1e6, 1),
+            "checked_over_plain_median": round(statistics.median(tc) / statistics.median(tp), 3)}
 
 
 def make_blocks(nconn, per_conn, fields_per_block, seed=7, index=False):
@@ -282,5 +390,7 @@ if __name__ == "__main__":
            "inflate_alt": bench_inflate_alt,
            "inflate_alt_index": lambda: bench_inflate_alt(index=True),
            "names": bench_names,
+           "check": bench_check,
+           "inflate_checked": bench_inflate_checked,
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
