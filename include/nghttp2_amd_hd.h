@@ -289,13 +289,36 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_huff_decode_fsm_batch(const uint8_t *src, 
  * reference's static_table[token].hash for a static name).  Device pointers,
  * asynchronous on `stream`.
  *
+ * nghttp2_amd_hd_name_tokens_len_batch: the same over strings with a length
+ * array, as nghttp2_amd_hd_check_fields_batch takes them.  len == NULL:
+ * string i = pool[off[i] .. off[i+1]).  len given: string i = pool[off[i] ..
+ * off[i] + len[i]) -- nghttp2_amd_hd_huff_decode_batch_auto's (dst, dst_off,
+ * status), tokenised in the decode's stream with no repacking.  off (n + 1
+ * entries) must be non-decreasing; the pool is 16-byte aligned and readable
+ * to align_up(off[n], 16) + 16.  A string gets NGHTTP2_AMD_TOKEN_INVALID and
+ * hash 0, and none of its bytes is read, when len[i] < 0 (a failed decode's
+ * status), off[i] + len[i] > off[i+1] (compared without wrapping) or off[i] >
+ * off[i+1]; NGHTTP2_AMD_TOKEN_NONE is lookup_token's -1: examined, not a
+ * token name.  Bytes outside a string never reach its token or hash.  hash
+ * may be NULL: only tokens are written, and a string longer than the longest
+ * token name gets NGHTTP2_AMD_TOKEN_NONE with none of its bytes read (with
+ * hash given every examined string is hashed in full).  Device pointers,
+ * asynchronous on `stream`; n == 0 returns 0, a NULL pool, off or token
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ *
  * nghttp2_amd_hd_lookup_token / nghttp2_amd_hd_name_hash: the same for one
  * host name (what a single deflate_nv call binds).
  */
+#define NGHTTP2_AMD_TOKEN_NONE (-1)
+#define NGHTTP2_AMD_TOKEN_INVALID (-2)
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_name_tokens_batch(const uint8_t *names,
                                                         const uint32_t *name_off, uint32_t n,
                                                         int32_t *token, uint32_t *hash,
                                                         void *stream);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_name_tokens_len_batch(const uint8_t *pool, const uint32_t *off,
+                                                            const int32_t *len, uint32_t n,
+                                                            int32_t *token, uint32_t *hash,
+                                                            void *stream);
 NGHTTP2_AMD_EXTERN int32_t nghttp2_amd_hd_lookup_token(const uint8_t *name, size_t namelen);
 NGHTTP2_AMD_EXTERN uint32_t nghttp2_amd_hd_name_hash(const uint8_t *name, size_t namelen);
 
@@ -433,6 +456,33 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_infl
                                   size_t nva_cap, size_t *nva_used, uint8_t *arena,
                                   size_t arena_cap, size_t *arena_used, int32_t *block_status,
                                   uint8_t *nv_checks, void *stream);
+
+/*
+ * nghttp2_amd_hd_inflate_blocks_checked that also hands every field over
+ * with its name token, as nghttp2_hd_inflate_hd_nv sets nv.token
+ * (lib/nghttp2_hd.c:1340, :1811): nv_tokens[k] = lookup_token of field k's
+ * name (NGHTTP2_AMD_TOKEN_NONE or NGHTTP2_TOKEN_*; nva_cap entries, the first
+ * *nva_used are written, for a block that ends in NGHTTP2_AMD_ERR_HEADER_COMP
+ * those of the fields emitted before the error).  Huffman-coded names are
+ * looked up on the GPU right behind their decode
+ * (nghttp2_amd_hd_name_tokens_len_batch over the decode's output with no
+ * hash: one more launch, behind the check launch when both are asked for,
+ * and four bytes per literal more in the copy back), raw names on the host
+ * inside the replay, static-table entries once per process; a dynamic-table
+ * entry carries its name's token from insertion (or from its first tokened
+ * reference, when a call without nv_tokens inserted it), so an indexed field
+ * or an indexed name costs no lookup.  nv_checks and nv_tokens are
+ * independent, either may be NULL: nv_tokens == NULL is
+ * nghttp2_amd_hd_inflate_blocks_checked, both NULL is
+ * nghttp2_amd_hd_inflate_blocks -- no token launch, no byte more in the
+ * copies, no host lookup.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_inflater *const *inflaters,
+                                  uint32_t nblocks, const uint8_t *const *blocks,
+                                  const size_t *block_lens, nghttp2_amd_hd_nv *nva,
+                                  size_t nva_cap, size_t *nva_used, uint8_t *arena,
+                                  size_t arena_cap, size_t *arena_used, int32_t *block_status,
+                                  uint8_t *nv_checks, int32_t *nv_tokens, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* Batched HPACK deflate front-end                                      */

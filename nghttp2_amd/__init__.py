@@ -23,6 +23,8 @@ from .hd import (  # noqa: F401
     NGHTTP2_ERR_HEADER_COMP,
     NGHTTP2_ERR_INSUFF_BUFSIZE,
     NGHTTP2_ERR_INVALID_ARGUMENT,
+    TOKEN_INVALID,
+    TOKEN_NONE,
     check_field,
     decode_length,
     lib,

@@ -30,6 +30,7 @@
 #include "../../include/nghttp2_amd_hd.h"
 #include "hd_field_classes.h"
 #include "hd_host.h"
+#include "hd_tokens.h"
 #include "host_threads.h"
 
 namespace {
@@ -49,13 +50,16 @@ const uint32_t kDefaultTable = 4096;   // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
 // An entry also carries the NGHTTP2_AMD_CHECK_* masks of its name and value
 // (kUnchecked until a checked call computes them: at insertion, or at the
 // first reference to an entry that an unchecked call inserted), so an indexed
-// field costs a checked call no byte scan.
+// field costs a checked call no byte scan.  The name's token (lookup_token)
+// travels the same way: kTokUnknown until a tokened call sets it.
 const uint8_t kUnchecked = NGHTTP2_AMD_CHECK_INVALID;
+const int8_t kTokUnknown = -3;  // (below NGHTTP2_AMD_TOKEN_INVALID; a token is -1..67)
 struct DynTable {
   struct Ent {
     size_t off;
     uint32_t nl, vl;
     uint8_t cn = kUnchecked, cv = kUnchecked;
+    int8_t tk = kTokUnknown;
   };
   std::vector<Ent> ents;   // ring, capacity a power of two
   size_t e_first = 0;      // oldest entry
@@ -102,7 +106,7 @@ struct DynTable {
     buf.swap(nb);
   }
   // n / v must not point into this table (the caller passes copies)
-  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv) {
+  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk) {
     if (count == ents.size()) {  // grow the descriptor ring, oldest first
       std::vector<Ent> ne(ents.empty() ? 16 : 2 * ents.size());
       for (size_t k = 0; k < count; ++k) ne[k] = ents[(e_first + k) & (ents.size() - 1)];
@@ -116,7 +120,7 @@ struct DynTable {
     }
     if (nl) memcpy(buf.data() + at, n, nl);
     if (vl) memcpy(buf.data() + at + nl, v, vl);
-    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, cn, cv};
+    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, cn, cv, tk};
     ++count;
   }
 };
@@ -146,12 +150,13 @@ struct nghttp2_amd_hd_inflater {
   // insert it unless it is larger than the whole table.  n / v are copies
   // outside the table (the caller's emitted field), so a name taken from an
   // entry that this insertion evicts stays valid, as in the reference.
-  // cn / cv: the field's check masks (kUnchecked from an unchecked call).
-  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv) {
+  // cn / cv: the field's check masks (kUnchecked from an unchecked call);
+  // tk: its name's token (kTokUnknown from a call without tokens).
+  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk) {
     const size_t room = nl + vl + kEntryOverhead;
     while (bufsize + room > bufsize_max && table.count) evict_oldest();
     if (room > bufsize_max) return;
-    table.push(n, nl, v, vl, cn, cv);
+    table.push(n, nl, v, vl, cn, cv, tk);
     bufsize += room;
     max_nl = std::max(max_nl, nl);
     max_vl = std::max(max_vl, vl);
@@ -190,6 +195,25 @@ struct nghttp2_amd_hd_inflater {
     if (e.cv == kUnchecked) e.cv = hdcls::check_field(table.value(e), e.vl);
     *cn = e.cn;
     *cv = e.cv;
+  }
+  // the token of entry idx's name (as entry()): the static table's are looked
+  // up once per process, a dynamic entry's is in its descriptor
+  int8_t entry_token(size_t idx) {
+    if (idx < kStaticLen) {
+      struct Tokens {
+        int8_t t[kStaticLen];
+      };
+      static const Tokens st = [] {
+        Tokens t;
+        for (uint32_t i = 0; i < kStaticLen; ++i)
+          t.t[i] = (int8_t)hdtok::lookup_token((const uint8_t *)kStatic[i][0], kStaticLens.len[i][0]);
+        return t;
+      }();
+      return st.t[idx];
+    }
+    DynTable::Ent &e = table.newest(idx - kStaticLen);
+    if (e.tk == kTokUnknown) e.tk = (int8_t)hdtok::lookup_token(table.name(e), e.nl);
+    return e.tk;
   }
 };
 
@@ -239,6 +263,7 @@ struct Rec {
   uint32_t name_off, name_len, value_off, value_len;
   uint8_t flags;
   uint8_t cn, cv;  // the check masks of name and value (a checked call)
+  int8_t tk;       // the name's token (a tokened call)
 };
 // A growable byte buffer written through a raw pointer (no per-append
 // capacity check or zero fill): a block's name\0value\0 runs.
@@ -275,7 +300,7 @@ struct Engine {
   std::mutex mu;
   PinnedBuf h_pool;  // Huffman literals in
   PinnedBuf h_out;   // decoded literals out
-  PinnedBuf h_meta;  // uint32: offsets in, then slots and status out ((nh + 1) each)
+  PinnedBuf h_meta;  // uint32: offsets in, then slots and status out ((nh + 1) each), tokens, masks
   DevBuf d_in, d_out, d_meta;  // their device copies (the modes that copy)
   std::vector<BlockOut> outs;
   // pass 1 state, kept across calls (under mu)
@@ -343,6 +368,7 @@ struct LitSrc {
   const uint32_t *slot;
   const int32_t *st;
   const uint8_t *chk;  // a checked call: the decoded literals' check masks (the GPU's)
+  const int32_t *tok;  // a tokened call: the decoded literals' tokens (the GPU's)
   // false: -523 (bad padding or EOS, hd_inflate_read_huff :1740-1750)
   bool get(const Lit &l, const char **p, size_t *n) const {
     if (l.huff < 0) {
@@ -359,6 +385,10 @@ struct LitSrc {
   // the check mask of a literal get() returned: a raw one is scanned here (on
   // the replay's thread), a Huffman one was scanned behind its decode
   uint8_t check(const Lit &l) const { return l.huff < 0 ? hdcls::check_field(l.p, l.len) : chk[l.huff]; }
+  // the token of a name literal get() returned, from the same two places
+  int8_t token(const Lit &l) const {
+    return (int8_t)(l.huff < 0 ? hdtok::lookup_token(l.p, l.len) : tok[l.huff]);
+  }
 };
 
 // What one dynamic-table reference of block b can emit (name + value): any
@@ -396,11 +426,12 @@ struct BlockSink {
     out.recs.clear();
     out.bytes.clear();
   }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv) {
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk) {
     Rec r;
     r.flags = flags;
     r.cn = cn;
     r.cv = cv;
+    r.tk = tk;
     r.name_off = (uint32_t)out.bytes.size();
     r.name_len = (uint32_t)nl;
     r.value_off = r.name_off + (uint32_t)nl + 1u;
@@ -423,14 +454,16 @@ struct DirectSink {
   nghttp2_amd_hd_nv *nva;
   int32_t *status;
   uint8_t *checks;  // the caller's nv_checks, or nullptr
+  int32_t *tokens;  // the caller's nv_tokens, or nullptr
   size_t ar = 0, nv = 0, nv0 = 0;
   uint32_t block = 0;
   void begin() { nv0 = nv; }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv) {
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk) {
     if (checks) {
       checks[2 * nv] = cn;
       checks[2 * nv + 1] = cv;
     }
+    if (tokens) tokens[nv] = tk;
     nghttp2_amd_hd_nv &d = nva[nv++];
     d.block = block;
     d.flags = flags;
@@ -452,8 +485,9 @@ struct DirectSink {
 };
 
 // chk: a checked call -- every emitted name and value with its check mask.
+// tok: a tokened call -- every emitted field with its name's token.
 template <class Sink>
-void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, bool chk, Sink &out) {
+void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, bool chk, bool tok, Sink &out) {
   out.begin();
   bool ok = !inf->bad;
   bool head = true;  // size updates only at the head of a block
@@ -478,6 +512,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     const char *n, *v;
     size_t nl, vl;
     uint8_t cn = kUnchecked, cv = kUnchecked;
+    int8_t tk = kTokUnknown;
     if (op.kind == Op::INDEXED) {  // hd_inflate_commit_indexed
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
@@ -485,7 +520,8 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       }
       inf->entry(op.value - 1, &n, &nl, &v, &vl);
       if (chk) inf->entry_checks(op.value - 1, &cn, &cv);
-      out.emit(n, nl, v, vl, 0, cn, cv);
+      if (tok) tk = inf->entry_token(op.value - 1);
+      out.emit(n, nl, v, vl, 0, cn, cv, tk);
       continue;
     }
     if (op.new_name) {  // hd_inflate_commit_newname
@@ -494,6 +530,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
         break;
       }
       if (chk) cn = ls.check(op.name);
+      if (tok) tk = ls.token(op.name);
     } else {  // hd_inflate_commit_indname
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
@@ -504,6 +541,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       inf->entry(op.value - 1, &n, &nl, &v0, &vl0);
       uint8_t cv0;
       if (chk) inf->entry_checks(op.value - 1, &cn, &cv0);
+      if (tok) tk = inf->entry_token(op.value - 1);
     }
     if (!ls.get(op.val, &v, &vl)) {
       ok = false;
@@ -511,9 +549,9 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     }
     if (chk) cv = ls.check(op.val);
     const uint8_t flags = op.no_index ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
-    out.emit(n, nl, v, vl, flags, cn, cv);
+    out.emit(n, nl, v, vl, flags, cn, cv, tk);
     if (op.index_required)  // the table copies the field just emitted
-      inf->add(out.last_name(), nl, out.last_value(), vl, cn, cv);
+      inf->add(out.last_name(), nl, out.last_value(), vl, cn, cv, tk);
   }
   // truncated or malformed wire after the parsed representations; and a
   // block that ends while a table size update is still expected
@@ -539,6 +577,7 @@ struct Dest {
   size_t arena_cap, *arena_used;
   int32_t *block_status;
   uint8_t *nv_checks;  // a checked call: two masks per field; else nullptr
+  int32_t *nv_tokens;  // a tokened call: a token per field; else nullptr
 };
 
 // The parts of a parsed block's output bound: a field per representation,
@@ -657,7 +696,13 @@ int zc_mode() {
 // A checked call queues nghttp2_amd_hd_check_fields_batch over the decode's
 // (dst, slots, status) right behind it; the masks, a byte per literal, sit
 // behind the status words and come back with them in the same copy.
-int stage_decode(Engine &E, uint32_t nblocks, bool checks, void *stream, Phases &ph, LitSrc *ls) {
+// A tokened call queues nghttp2_amd_hd_name_tokens_len_batch (no hash: a
+// literal longer than every token name is not read) over the same three
+// arrays behind that; the tokens, an int32 per literal, sit between the status
+// words and the masks and come back in that copy too.  Values get a token as
+// names do (pass 1 numbers the literals without telling them apart); the
+// replay reads the names' only.
+int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, void *stream, Phases &ph, LitSrc *ls) {
   for (uint32_t i = 0; i < nblocks; ++i) {
     E.nhuff[i + 1] += E.nhuff[i];
     E.hbytes[i + 1] += E.hbytes[i];
@@ -674,9 +719,12 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, void *stream, Phases 
   const size_t in_bytes = ((size_t)hb + 15u) / 16u * 16u + 16u;
   const size_t out_bytes = nh ? nghttp2_amd_hd_huff_decode_bound(hb, nh) : 0;
   // (the check reads whole 16-byte chunks up to the last slot's end, and one
-  // at it when every literal is empty)
-  const size_t out_alloc = out_bytes + (checks ? 16u : 0u);
-  const size_t slots = (size_t)nh + 1u, meta = 3u * slots * sizeof(uint32_t) + (checks ? nh : 0u);
+  // at it when every literal is empty; the token lookup reads at most one
+  // chunk past the chunk a literal ends in)
+  const size_t out_alloc = out_bytes + (checks || tokens ? 16u : 0u);
+  // behind the status words: [tokens: nh int32] [checks: nh bytes]
+  const size_t tok_bytes = tokens ? nh * sizeof(int32_t) : 0u, chk_bytes = checks ? nh : 0u;
+  const size_t slots = (size_t)nh + 1u, meta = 3u * slots * sizeof(uint32_t) + tok_bytes + chk_bytes;
   // (the output pool is a D2H copy target unless the kernel writes it
   // through the mapping, mode 1; the input pools are mapped unless mode 0;
   // mode 2 needs no device copy of the input)
@@ -688,7 +736,7 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, void *stream, Phases 
   ph.mark("pools");
   number_and_copy(E, nblocks);
   ph.mark("number+copy");
-  *ls = LitSrc{nullptr, nullptr, nullptr, nullptr};
+  *ls = LitSrc{nullptr, nullptr, nullptr, nullptr, nullptr};
   if (!nh) return 0;
   hipStream_t st = (hipStream_t)stream;
   uint32_t *const h_meta = E.h_meta.as<uint32_t>();
@@ -721,7 +769,12 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, void *stream, Phases 
                                                        nullptr, nullptr, stream);
   if (rv) return drain(rv);
   if (checks) {
-    const int rc = nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, (uint8_t *)(d_st + nh), stream);
+    const int rc =
+        nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, (uint8_t *)(d_st + nh) + tok_bytes, stream);
+    if (rc) return drain(rc);
+  }
+  if (tokens) {
+    const int rc = nghttp2_amd_hd_name_tokens_len_batch(dst, d_slot, d_st, nh, d_st + nh, nullptr, stream);
     if (rc) return drain(rc);
   }
   uint32_t *h_slot = h_meta + slots;
@@ -729,10 +782,11 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, void *stream, Phases 
   if (!zero_copy &&
       (hipMemcpyAsync(E.h_out.p, dst, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
        hipMemcpyAsync(h_slot, d_slot, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t) + (checks ? nh : 0u), hipMemcpyDeviceToHost, st) !=
+       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t) + tok_bytes + chk_bytes, hipMemcpyDeviceToHost, st) !=
            hipSuccess))
     return drain(NGHTTP2_AMD_ERR_FATAL);
-  *ls = LitSrc{E.h_out.as<uint8_t>(), h_slot, h_st, checks ? (const uint8_t *)(h_st + nh) : nullptr};
+  *ls = LitSrc{E.h_out.as<uint8_t>(), h_slot, h_st, checks ? (const uint8_t *)(h_st + nh) + tok_bytes : nullptr,
+               tokens ? h_st + nh : nullptr};
   return 0;
 }
 
@@ -784,7 +838,7 @@ bool may_cut(const Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
 
 // One replayed block's fields into the caller's field array at nv_base and arena at ar_base.
 void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_base, nghttp2_amd_hd_nv *nva,
-                 uint8_t *arena, uint8_t *checks) {
+                 uint8_t *arena, uint8_t *checks, int32_t *tokens) {
   const uint32_t ab = (uint32_t)ar_base;
   if (!o.bytes.empty()) memcpy(arena + ab, o.bytes.data(), o.bytes.size());
   nghttp2_amd_hd_nv *d = nva + nv_base;
@@ -793,6 +847,10 @@ void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_ba
   if (checks) {
     uint8_t *c = checks + 2 * nv_base;
     for (const Rec &r : o.recs) *c++ = r.cn, *c++ = r.cv;
+  }
+  if (tokens) {
+    int32_t *t = tokens + nv_base;
+    for (const Rec &r : o.recs) *t++ = r.tk;
   }
 }
 
@@ -806,8 +864,8 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
   if (ls.st && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
   ph.mark("gpu wait");
   nghttp2_amd_hd_inflater *c = E.conns[0];
-  DirectSink ds{d.arena, d.nva, d.block_status, d.nv_checks};
-  const bool chk = d.nv_checks != nullptr;
+  DirectSink ds{d.arena, d.nva, d.block_status, d.nv_checks, d.nv_tokens};
+  const bool chk = d.nv_checks != nullptr, tok = d.nv_tokens != nullptr;
   uint32_t cut = nblocks;
   for (uint32_t i = 0; i < nblocks; ++i) {
     const Block &b = E.bl[i];
@@ -816,19 +874,19 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
     const uint64_t ar_b = block_ar_bound(b, dyn_ref_bound(c, b.lit_name, b.lit_val));
     ds.block = i;
     if (ds.nv + b.nv <= d.nva_cap && ar_b <= d.arena_cap - ds.ar) {
-      replay_block(c, b, ls, chk, ds);
+      replay_block(c, b, ls, chk, tok, ds);
       continue;
     }
     nghttp2_amd_hd_inflater keep = *c;
     BlockOut scratch;
     BlockSink bs{scratch};
-    replay_block(c, b, ls, chk, bs);
+    replay_block(c, b, ls, chk, tok, bs);
     if (ds.nv + scratch.recs.size() > d.nva_cap || scratch.bytes.size() > d.arena_cap - ds.ar) {
       *c = std::move(keep);
       cut = i;
       break;
     }
-    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena, d.nv_checks);
+    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena, d.nv_checks, d.nv_tokens);
     ds.nv += scratch.recs.size();
     ds.ar += scratch.bytes.size();
     d.block_status[i] = scratch.status;
@@ -859,11 +917,11 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
   // replay allocates only while they grow
   std::vector<BlockOut> &outs = E.outs;
   if (outs.size() < nblocks) outs.resize(nblocks);
-  const bool chk = d.nv_checks != nullptr;
+  const bool chk = d.nv_checks != nullptr, tok = d.nv_tokens != nullptr;
   parallel_for(conns.size(), 1, [&](size_t c) {
     for (uint32_t j = E.cstart[c]; j < E.cstart[c + 1]; ++j) {
       BlockSink bs{outs[E.corder[j]]};
-      replay_block(conns[c], E.bl[E.corder[j]], ls, chk, bs);
+      replay_block(conns[c], E.bl[E.corder[j]], ls, chk, tok, bs);
     }
   });
   ph.mark("replay");
@@ -891,11 +949,11 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
     for (size_t c = 0; c < conns.size(); ++c) *conns[c] = std::move(snap[c]);
     BlockOut scratch;
     BlockSink ss{scratch};
-    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], E.bl[i], ls, chk, ss);
+    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], E.bl[i], ls, chk, tok, ss);
     for (uint32_t j = cut; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
   }
   parallel_for(cut, 256, [&](size_t i) {
-    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena, d.nv_checks);
+    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena, d.nv_checks, d.nv_tokens);
     d.block_status[i] = outs[i].status;
   });
   ph.mark("place");
@@ -1013,6 +1071,16 @@ int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_inflater *const *inflat
                                           nghttp2_amd_hd_nv *nva, size_t nva_cap, size_t *nva_used,
                                           uint8_t *arena, size_t arena_cap, size_t *arena_used,
                                           int32_t *block_status, uint8_t *nv_checks, void *stream) {
+  return nghttp2_amd_hd_inflate_blocks_fields(inflaters, nblocks, blocks, block_lens, nva, nva_cap, nva_used, arena,
+                                              arena_cap, arena_used, block_status, nv_checks, nullptr, stream);
+}
+
+int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks,
+                                         const uint8_t *const *blocks, const size_t *block_lens,
+                                         nghttp2_amd_hd_nv *nva, size_t nva_cap, size_t *nva_used,
+                                         uint8_t *arena, size_t arena_cap, size_t *arena_used,
+                                         int32_t *block_status, uint8_t *nv_checks, int32_t *nv_tokens,
+                                         void *stream) {
   if (nva_used) *nva_used = 0;
   if (arena_used) *arena_used = 0;
   if (nblocks == 0) return 0;
@@ -1025,11 +1093,11 @@ int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_inflater *const *inflat
   Phases ph("inflate");
   std::lock_guard<std::mutex> guard(engine().mu);
   Engine &E = engine();
-  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status, nv_checks};
+  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status, nv_checks, nv_tokens};
   parse_blocks(E, nblocks, blocks, block_lens);
   ph.mark("parse blocks");
   LitSrc ls;
-  if (const int rv = stage_decode(E, nblocks, nv_checks != nullptr, stream, ph, &ls)) return rv;
+  if (const int rv = stage_decode(E, nblocks, nv_checks != nullptr, nv_tokens != nullptr, stream, ph, &ls)) return rv;
   ph.mark("gpu issued");
   // (the decode runs while the host groups the blocks by connection and
   // bounds the output; replay waits for it)

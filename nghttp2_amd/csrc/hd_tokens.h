@@ -55,6 +55,16 @@ constexpr uint32_t cstr_len(const char *s) {
   while (s[n]) ++n;
   return n;
 }
+// the longest name lookup_token knows: a longer string is no token name,
+// whatever its bytes
+constexpr uint32_t max_token_len() {
+  uint32_t m = 0;
+  for (uint32_t k = 0; k < kNumTokens; ++k)
+    if (cstr_len(kTokens[k].name) > m) m = cstr_len(kTokens[k].name);
+  return m;
+}
+constexpr uint32_t kMaxTokenLen = max_token_len();
+static_assert(kMaxTokenLen <= 32u, "the kernel's token compare holds a name of at most 32 bytes");
 constexpr uint32_t fnv1a(const char *s, uint32_t n) {
   uint32_t h = kFnvBasis;
   for (uint32_t i = 0; i < n; ++i) {
@@ -120,6 +130,11 @@ inline int32_t lookup_token(const uint8_t *p, size_t n, uint32_t h) {
     while (i < n && q[i] == p[i]) ++i;
     if (i == n) return (int32_t)meta_token(m);
   }
+}
+// The token alone (the inflater's lookup, lib/nghttp2_hd.c:1811): a string
+// longer than every token name is not hashed.
+inline int32_t lookup_token(const uint8_t *p, size_t n) {
+  return n > kMaxTokenLen ? -1 : lookup_token(p, n, name_hash(p, n));
 }
 
 }  // namespace hdtok

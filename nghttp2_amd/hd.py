@@ -44,6 +44,10 @@ CHECK_AUTHORITY = 0x20        # nghttp2_check_authority
 CHECK_NAME_LOWER = 0x40       # nghttp2_check_nonempty_header_name(...) == 1
 CHECK_INVALID = 0x80          # the string was not examined
 
+# name_tokens / inflate_blocks(tokens=True): lookup_token's result, or
+TOKEN_NONE = -1               # examined, not a token name (lookup_token's -1)
+TOKEN_INVALID = -2            # the string was not examined
+
 _lib = None
 
 
@@ -93,6 +97,7 @@ def lib():
         L.nghttp2_amd_hd_emit_strings_workspace_size.argtypes = [u64, u32]
         L.nghttp2_amd_hd_emit_strings_batch.argtypes = [vp, vp, u32, u64, vp, sz, vp, vp, sz, vp]
         L.nghttp2_amd_hd_name_tokens_batch.argtypes = [vp, vp, u32, vp, vp, vp]
+        L.nghttp2_amd_hd_name_tokens_len_batch.argtypes = [vp, vp, vp, u32, vp, vp, vp]
         L.nghttp2_amd_hd_lookup_token.argtypes = [ctypes.c_char_p, sz]
         L.nghttp2_amd_hd_lookup_token.restype = ctypes.c_int32
         L.nghttp2_amd_hd_name_hash.argtypes = [ctypes.c_char_p, sz]
@@ -231,14 +236,28 @@ class HuffmanBatchCodec:
         _check(rv, "encode_count_batch")
         return enc_len[:n]
 
-    def name_tokens(self, names, name_off, token=None, hash=None, stream=None):
+    def name_tokens(self, names, name_off, token=None, hash=None, stream=None, len=None,
+                    want_hash=True):
         """lookup_token + name_hash (lib/nghttp2_hd.c:137, :536) for every
         name of the batch: returns (token int32[n], hash int32[n] holding the
-        uint32 FNV-1a bits)."""
+        uint32 FNV-1a bits).  With len (int32[n], e.g. decode_auto's status
+        next to its dst and dst_off) name i is names[off[i]:off[i]+len[i]]; a
+        name with a negative or overrunning len gets TOKEN_INVALID and hash 0.
+        With want_hash=False only the tokens are computed and returned, and a
+        string longer than every token name is not read.  Either of the two
+        goes through nghttp2_amd_hd_name_tokens_len_batch."""
         torch = self.torch
         n = name_off.numel() - 1
         if token is None:
             token = self._empty(max(1, n), torch.int32, stream)
+        if len is not None or not want_hash:
+            if want_hash and hash is None:
+                hash = self._empty(max(1, n), torch.int32, stream)
+            rv = self.L.nghttp2_amd_hd_name_tokens_len_batch(
+                _p(names), _p(name_off), _p(len), n, _p(token), _p(hash if want_hash else None),
+                _stream(stream))
+            _check(rv, "name_tokens_len_batch")
+            return (token[:n], hash[:n]) if want_hash else token[:n]
         if hash is None:
             hash = self._empty(max(1, n), torch.int32, stream)
         rv = self.L.nghttp2_amd_hd_name_tokens_batch(
@@ -409,6 +428,9 @@ def _inflate_lib():
         L.nghttp2_amd_hd_inflate_blocks_checked.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, sz,
                                                             ctypes.POINTER(sz), vp, sz,
                                                             ctypes.POINTER(sz), vp, vp, vp]
+        L.nghttp2_amd_hd_inflate_blocks_fields.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, sz,
+                                                           ctypes.POINTER(sz), vp, sz,
+                                                           ctypes.POINTER(sz), vp, vp, vp, vp]
         L._inflate_bound = True
     return L
 
@@ -464,7 +486,7 @@ assert _NV_DTYPE.itemsize == ctypes.sizeof(_Nv)
 
 
 def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None, retry=True,
-                   checks=False):
+                   checks=False, tokens=False):
     """Inflate complete header blocks, block i against inflaters[i], with
     every Huffman literal decoded in one GPU batch.  Returns
     (status[i], fields[i] = [(name, value, flags)]).  A batch that outgrows
@@ -474,6 +496,10 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
     With checks the call is nghttp2_amd_hd_inflate_blocks_checked and a third
     result follows: a uint8 array (nfields, 2) of the CHECK_* masks of every
     emitted field's name and value, in the order of the fields.
+    With tokens the call is nghttp2_amd_hd_inflate_blocks_fields and one more
+    result follows (after the masks when both are asked for): an int32 array
+    (nfields,) of lookup_token of every emitted field's name, as
+    nghttp2_hd_inflate_hd_nv sets nv.token.
     The blocks go in as one joined buffer and the fields come out of
     uninitialised numpy buffers (no per-block ctypes objects, no zero fill)."""
     L = _inflate_lib()
@@ -501,7 +527,7 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
             s = None
     status = [NGHTTP2_ERR_BUFFER_ERROR] * nb
     fields = [[] for _ in range(nb)]
-    masks = []
+    masks, toks = [], []
     first = 0
     vp = ctypes.c_void_p
     while first < nb:
@@ -513,7 +539,15 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
         arena = np.empty(max(1, arena_cap), dtype=np.uint8)
         st = np.empty(m, dtype=np.int32)
         nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
-        if checks:
+        if tokens:
+            chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8) if checks else None
+            tk = np.empty(max(1, nva_cap), dtype=np.int32)
+            rv = L.nghttp2_amd_hd_inflate_blocks_fields(
+                vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
+                vp(nva.ctypes.data), nva_cap, ctypes.byref(nv_used), vp(arena.ctypes.data),
+                arena_cap, ctypes.byref(ar_used), vp(st.ctypes.data),
+                vp(chk.ctypes.data) if checks else None, vp(tk.ctypes.data), s)
+        elif checks:
             chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8)
             rv = L.nghttp2_amd_hd_inflate_blocks_checked(
                 vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
@@ -530,6 +564,8 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
         nv = nva[:nv_used.value]
         if checks:
             masks.append(chk[:nv_used.value].copy())
+        if tokens:
+            toks.append(tk[:nv_used.value].copy())
         for b, no, nl, vo, vl, fl in zip((nv["block"] + first).tolist(), nv["name_off"].tolist(),
                                          nv["name_len"].tolist(), nv["value_off"].tolist(),
                                          nv["value_len"].tolist(), nv["flags"].tolist()):
@@ -545,9 +581,12 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
                 break
             if done == 0:
                 nva_cap, arena_cap = 2 * nva_cap + 16, 2 * arena_cap + 4096
+    res = (status, fields)
     if checks:
-        return status, fields, (np.concatenate(masks) if masks else np.zeros((0, 2), np.uint8))
-    return status, fields
+        res += (np.concatenate(masks) if masks else np.zeros((0, 2), np.uint8),)
+    if tokens:
+        res += (np.concatenate(toks) if toks else np.zeros(0, np.int32),)
+    return res
 
 
 # ---------------------------------------------------------------------------

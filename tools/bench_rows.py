@@ -20,6 +20,17 @@
   inflate_checked  nghttp2_amd_hd_inflate_blocks_checked against
            nghttp2_amd_hd_inflate_blocks on the 2,048-block batch, alternated:
            what the check launch and the mask bytes in the copy back cost.
+  names_len  nghttp2_amd_hd_name_tokens_len_batch against
+           nghttp2_amd_hd_name_tokens_batch on the 1M names, alternated call by
+           call (the len form with a hash: the same walk plus one load per
+           lane), and its hash-free form on 1M mixed values: what the early
+           exit leaves of a pool of strings that are mostly no names.
+  inflate_fields  nghttp2_amd_hd_inflate_blocks_fields with both arrays
+           against nghttp2_amd_hd_inflate_blocks_checked on the 2,048-block
+           batch, alternated; and with NGHTTP2_AMD_OTHER_LIB naming another
+           build of the library (the parent commit's), its _checked against
+           this build's in the same process: the existing call must not have
+           become slower.
 
 Prints one JSON object.  Not the bench.py contract (that is the hot path
 itself); the numbers go to DESIGN.md."""
@@ -165,6 +176,159 @@ def bench_check(steps=30):
                       "count_GBps_R_plus_5N": round(B / te / 1e9, 1),
                       "check_us_median": round(float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e3, 2),
                       "encode_count_us_median": round(float(np.median([e[2].elapsed_time(e[3]) for e in ev])) * 1e3, 2)}
+    return out
+
+
+def bench_names_len(steps=30):
+    """The three forms alternated call by call on device-resident pools, each
+    call between two HIP events, best and median of the steps."""
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import workloads as W
+    from oracle import hpack_oracle as H
+    dev = torch.device("cuda:0")
+    codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    s = torch.cuda.current_stream()
+    n = 1 << 20
+
+    def timed(calls):
+        for _ in range(5):
+            for c in calls.values():
+                c()
+        ev = {k: [] for k in calls}
+        for _ in range(steps):
+            for k, c in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(s)
+                c()
+                b.record(s)
+                ev[k].append((a, b))
+        torch.cuda.synchronize()
+        out = {}
+        for k, v in ev.items():
+            t = [a.elapsed_time(b) * 1e3 for a, b in v]
+            out[k + "_us_best"] = round(min(t), 2)
+            out[k + "_us_median"] = round(float(np.median(t)), 2)
+        return out
+
+    pool, off = W.gen_names(n)
+    raw = int(off[-1])
+    names = torch.from_numpy(pool).to(dev)
+    no = torch.from_numpy(off.view(np.int32)).to(dev)
+    ln = torch.from_numpy(np.diff(off.astype(np.int64)).astype(np.int32)).to(dev)
+    tok, h = codec.name_tokens(names, no)
+    tok2, h2 = codec.name_tokens(names, no, len=ln)
+    tok3 = codec.name_tokens(names, no, len=ln, want_hash=False)
+    torch.cuda.synchronize()
+    assert torch.equal(tok, tok2) and torch.equal(h, h2) and torch.equal(tok, tok3)
+    k = 20000  # parity on a sample
+    et, _ = H.name_tokens([pool[off[i]:off[i + 1]].tobytes() for i in range(k)])
+    assert np.array_equal(tok3[:k].cpu().numpy(), np.array(et, np.int32))
+    rows = {"names_1M": {"names": n, "name_bytes": raw, **timed({
+        "old": lambda: codec.name_tokens(names, no, token=tok, hash=h),
+        "len_hash": lambda: codec.name_tokens(names, no, token=tok2, hash=h2, len=ln),
+        "len_nohash": lambda: codec.name_tokens(names, no, token=tok3, len=ln, want_hash=False)})}}
+    r = rows["names_1M"]
+    r["len_hash_over_old_best"] = round(r["len_hash_us_best"] / r["old_us_best"], 3)
+    r["len_hash_over_old_median"] = round(r["len_hash_us_median"] / r["old_us_median"], 3)
+    pool, off = W.gen_mixed_range(W.mixed_lengths(n), 0, n, threads=8)
+    raw = int(off[-1])
+    src = torch.from_numpy(pool).to(dev)
+    so = torch.from_numpy(off.view(np.int32)).to(dev)
+    ln = torch.from_numpy(np.diff(off.astype(np.int64)).astype(np.int32)).to(dev)
+    tv = codec.name_tokens(src, so, len=ln, want_hash=False)
+    tvh, hv = codec.name_tokens(src, so, len=ln)
+    torch.cuda.synchronize()
+    assert torch.equal(tv, tvh)
+    rows["mixed_values_1M"] = {"strings": n, "raw_bytes": raw,
+                               "strings_up_to_max_token_len": int((ln <= 27).sum().item()), **timed({
+                                   "len_nohash": lambda: codec.name_tokens(src, so, token=tv, len=ln, want_hash=False),
+                                   "len_hash": lambda: codec.name_tokens(src, so, token=tvh, hash=hv, len=ln)})}
+    return rows
+
+
+def bench_inflate_fields(nconn=256, per_conn=8, fields=16, alternations=15):
+    """The C call of the 2,048-block inflate row, alternated call by call (no
+    indexing: every call sees the same tables): plain, checked, tokens and
+    both arrays; with NGHTTP2_AMD_OTHER_LIB, that build's checked call too."""
+    import ctypes
+    import statistics
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    blocks, conns = make_blocks(nconn, per_conn, fields)
+    wire = sum(len(b) for b in blocks)
+    L = hd._inflate_lib()
+    m = len(blocks)
+    keep = [ctypes.create_string_buffer(b, len(b)) for b in blocks]
+    ptrs = (ctypes.c_void_p * m)(*[ctypes.cast(k, ctypes.c_void_p) for k in keep])
+    lens = (ctypes.c_size_t * m)(*[len(b) for b in blocks])
+    nva_cap, arena_cap = wire + 16, 8 * wire + 4096
+    nva = (hd._Nv * nva_cap)()
+    arena = (ctypes.c_uint8 * arena_cap)()
+    chk = (ctypes.c_uint8 * (2 * nva_cap))()
+    tk = (ctypes.c_int32 * nva_cap)()
+    stc = (ctypes.c_int32 * m)()
+    nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
+    import torch
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+    ip = (ctypes.c_void_p * m)(*[infs[c].p.value for c in conns])
+    calls = {}
+
+    def fields_call(c, t):
+        def f():
+            t0 = time.perf_counter()
+            rv = L.nghttp2_amd_hd_inflate_blocks_fields(ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used),
+                                                        arena, arena_cap, ctypes.byref(ar_used), stc, c, t, s)
+            dt = time.perf_counter() - t0
+            assert rv == 0
+            return dt
+        return f
+    calls["plain"] = fields_call(None, None)
+    calls["checked"] = fields_call(chk, None)
+    calls["tokens"] = fields_call(None, tk)
+    calls["fields"] = fields_call(chk, tk)
+    other = os.environ.get("NGHTTP2_AMD_OTHER_LIB")
+    if other:
+        P = ctypes.CDLL(other)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        P.nghttp2_amd_hd_inflate_new.argtypes = [ctypes.POINTER(vp)]
+        P.nghttp2_amd_hd_inflate_blocks_checked.argtypes = L.nghttp2_amd_hd_inflate_blocks_checked.argtypes
+        pin = []
+        for _ in range(nconn):
+            q = vp()
+            assert P.nghttp2_amd_hd_inflate_new(ctypes.byref(q)) == 0
+            pin.append(q.value)
+        pip = (ctypes.c_void_p * m)(*[pin[c] for c in conns])
+
+        def other_checked():
+            t0 = time.perf_counter()
+            rv = P.nghttp2_amd_hd_inflate_blocks_checked(pip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used),
+                                                         arena, arena_cap, ctypes.byref(ar_used), stc, chk, s)
+            dt = time.perf_counter() - t0
+            assert rv == 0
+            return dt
+        calls["other_checked"] = other_checked
+    for _ in range(3):
+        for c in calls.values():
+            c()
+    ts = {k: [] for k in calls}
+    for _ in range(alternations):
+        for k, c in calls.items():
+            ts[k].append(c())
+    nf = nv_used.value
+    out = {"blocks": m, "connections": nconn, "fields": nf, "wire_bytes": wire, "alternations": alternations}
+    for k, v in ts.items():
+        out[k + "_s_best"] = round(min(v), 6)
+        out[k + "_s_median"] = round(statistics.median(v), 6)
+        out[k + "_s_worst"] = round(max(v), 6)
+    out["fields_minus_checked_us_median"] = round((out["fields_s_median"] - out["checked_s_median"]) * 1e6, 1)
+    out["fields_minus_checked_us_best"] = round((out["fields_s_best"] - out["checked_s_best"]) * 1e6, 1)
+    if other:
+        out["checked_minus_other_checked_us_median"] = round(
+            (out["checked_s_median"] - out["other_checked_s_median"]) * 1e6, 1)
+        out["checked_minus_other_checked_us_best"] = round(
+            (out["checked_s_best"] - out["other_checked_s_best"]) * 1e6, 1)
     return out
 
 
@@ -392,5 +556,7 @@ if __name__ == "__main__":
            "names": bench_names,
            "check": bench_check,
            "inflate_checked": bench_inflate_checked,
+           "names_len": bench_names_len,
+           "inflate_fields": bench_inflate_fields,
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
