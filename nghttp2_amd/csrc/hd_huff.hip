@@ -1568,13 +1568,22 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
 #define DD_TAILU 2u  // the workgroup's last DD_TAILU x waves units are claimed singly
 #endif
 #ifndef DD_SK40
-#define DD_SK40 2u  // the 40-byte instance serves long codes every 2nd pair (dd_run SLOWK)
+#define DD_SK40 2u  // the 40-byte instance's serving period in pairs (dd_run SLOWK; unused while DD_LD40 defers its long codes)
 #endif
 #ifndef DD_DIRECT_MIN
 #define DD_DIRECT_MIN 4u  // lanes of a round with long codes that switch the wave's next round to direct
 #endif
 #ifndef DD_DIRECT_KEEP
 #define DD_DIRECT_KEEP 4u  // ... and to keep it on for the round after
+#endif
+#ifndef DD_LD40
+#define DD_LD40 1u  // the 40-byte instance's long codes in the pair loop (dd_run LDEF): 0 served, 1 deferred, 2 deferred in two-pair trips
+#endif
+#ifndef DD_LDW40
+#define DD_LDW40 1u  // ... and in its warm-ups too (0: warm-ups keep the served form)
+#endif
+#ifndef DD_DEFW
+#define DD_DEFW 15u  // a deferred long code of up to DD_DEFW bits is followed by the pair's second lookup
 #endif
 #ifndef DD_SK64
 #define DD_SK64 1u  // the 64-byte instance (config 5's 30-bit codes everywhere): every pair
@@ -1588,10 +1597,12 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
 struct DecHeader {  // header strings: whole strings as items, budgeted rounds
   static constexpr uint32_t IP = DD_IP64, BI = DD_BI64, SK = DD_SK64, TS = DD_TS64, TK = DD_TK64;
   static constexpr int IW = DD_IW64, LB = DD_LB64;
+  static constexpr uint32_t LD = 0, LDW = 0;
 };
 struct DecLong {  // long values: 40-byte pieces, ranges balanced by weight
   static constexpr uint32_t IP = DD_IP40, BI = DD_BI40, SK = DD_SK40, TS = DD_TS40, TK = DD_TK40;
   static constexpr int IW = DD_IW40, LB = DD_LB40;
+  static constexpr uint32_t LD = DD_LD40, LDW = DD_LDW40 ? DD_LD40 : 0u;
 };
 
 // The output region of an item of `bytes` input bytes (<= (8 bytes + 29) / 5
@@ -1702,9 +1713,13 @@ struct DDRun {
 // needs its 14 lookup bits inside the string (bp + 14 <= bend) and must not
 // pass the first boundary >= bstop (bp <= bstop - 13: the first symbol of a
 // 2-symbol entry is <= 9 bits); pairs run while both steps qualify.  A code
-// longer than the lookup (entry 0) stalls the lane for the rest of the pair,
-// then goes through long_entry; one that would pass the string end is its
-// tail and leaves the fast loop.  The last bits go through checked steps,
+// longer than the lookup (entry 0) stalls the lane for the rest of the pair.
+// The 40-byte instance (LDEF) then reads it from the leading-ones table as
+// the lane's next pair's first read (deferred: no serving block, no third
+// dependent read, no further stall; `pair_def` below).  The 64-byte instance
+// sends it through long_entry in a block the wave runs every SLOWK-th pair,
+// or decodes it directly (kDirect); there, one that would pass the string
+// end is its tail and leaves the fast loop.  The last bits go through checked steps,
 // which also settle the tail: the undecoded t < 30 bits.
 #define DD_ADV(U)                                                        \
   do {                                                                   \
@@ -1719,7 +1734,8 @@ struct DDRun {
 // PAIRS: only the fast pairs, none starting past `lim` (no careful steps):
 // bp stops at a codeword boundary on the way, for a caller that records it
 // and goes on with another dd_run.
-template <class Sink, bool SYNC = false, bool PAIRS = false, uint32_t SLOWK = 1, class TT, class IN>
+template <class Sink, bool SYNC = false, bool PAIRS = false, uint32_t SLOWK = 1, uint32_t LDEF = 0,
+          class TT, class IN>
 __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
                                         uint32_t bstop, uint32_t bend, Sink &sink,
                                         int32_t lim = INT32_MAX, bool direct = false,
@@ -1736,7 +1752,14 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   // (SYNC, a warm-up: pairs may pass bstop -- the first boundary at or after
   // it is then one of the last pair's, picked after the loop; the same
   // overshoot for the items' own decode measured slower: 314.5 vs 303.6 us)
-  int32_t G2 = min((int32_t)bstop - (SYNC ? 1 : 2 * TT::BITS - 4), (int32_t)bend - 2 * TT::BITS);
+  // (LDEF: a deferred long code of up to DD_DEFW bits is followed by a
+  // lookup, a longer one by nothing; one of 30 bits ends inside the string)
+  constexpr int32_t kSecond = (LDEF && (int)DD_DEFW > TT::BITS) ? (int)DD_DEFW : TT::BITS;
+  constexpr int32_t kStopB = kSecond + TT::BITS - 4;
+  constexpr int32_t kEndB = (LDEF && kSecond + TT::BITS < 30) ? 30 : kSecond + TT::BITS;
+  static_assert(!LDEF || (DD_DEFW + TT::BITS < 32u && DD_DEFW >= (uint32_t)TT::BITS),
+                "a pair advances < 32 bits (DD_ADV); a lookup entry is never taken for a long one");
+  int32_t G2 = min((int32_t)bstop - (SYNC ? 1 : kStopB), (int32_t)bend - kEndB);
   if (PAIRS) G2 = min(G2, lim);
   // (SYNC) the last pair: start (as nq), entries, slow code
   uint32_t pb = ~(bp - 1u), le1 = 0, le2 = 0, ls = 0;
@@ -1836,8 +1859,75 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
       }
     }
   };
+  // deferred (LDEF): a lane whose second lookup returned 0 -- its first one
+  // did too, then, the window unchanged -- keeps the index of the long code
+  // at its new window, computed at the pair's end off the next pair's chain,
+  // and its next pair's first read goes to the leading-ones table instead
+  // of the lookup: no serving block, no third dependent read, no stall.  The
+  // entry has the lookup's layout (one symbol, used = L1 = its length).  A
+  // pair starts at most 30 bits before the string end, so the long code
+  // ends inside the string; EOS (30 ones: the table's last two rows) is not
+  // deferred, the lane leaves the loop and the careful steps fail it.  The
+  // pair's second lookup needs its bits inside the window and its codes to
+  // start before bstop: it follows a long code of up to DD_DEFW bits (the
+  // bounds above), after a longer one the lane takes nothing (E_EOS: an
+  // entry of no symbols and no bits that is not 0).
+  // The window and the first read's address are carried from the end of
+  // the pair before.  A lane with a long code there has n1 = 12..29 leading
+  // ones (the lookup is 0 only for such a prefix; 30 and more: EOS), so its
+  // index needs none of long_index's clamps: the signed leading-bit count
+  // (-1 for all ones: as unsigned past 30) and, the ones shifted out, the
+  // zero and five bits on top.  (Config 3 decode 194.4 / 193.9 / 195.6 vs
+  // the serving form's 216.7 / 214.6 / 213.4 us in three interleaved sets,
+  // outputs equal, configs 2 and 5 flat; with long_index, a flag and the
+  // select at the pair's head 208.5 / 211.3 / 213.0 vs 210.8 / 213.1 / 214.1;
+  // two-pair trips 200.7 / 197.6 / 197.5; warm-ups left on the serving form
+  // 201.1 / 198.1 / 200.0 -- profiles/long_codes_deferred/)
+  // (one table base and an index select: the tables are adjacent words)
+  static_assert(offsetof(TT, lut) == 0 && offsetof(TT, long1) == sizeof(uint32_t) << TT::BITS, "tables adjacent");
+  const uint32_t *tw = T.lut;
+  uint32_t dw = __builtin_amdgcn_alignbit(A, B, nq);
+  uint32_t di = dw >> (32 - TT::BITS);
+  auto pair_def = [&]() {
+    const uint32_t e1 = tw[di];
+    const uint32_t U1 = E_USED(e1);
+    uint32_t e2 = T.lut[(dw << U1) >> (32 - TT::BITS)];
+    e2 = U1 > DD_DEFW ? E_EOS : e2;
+    sink.put2(e1, e2);
+    const uint32_t U2 = E_USED(e2);
+    if (SYNC) {
+      pb = nq;  // (as bp after the loop)
+      le1 = e1;
+      le2 = e2;
+    }
+    DD_ADV(U1 + U2);
+    dw = __builtin_amdgcn_alignbit(A, B, nq);
+    // (the signed leading-bit count has no builtin; the index is made
+    // opaque so that the select stays a select: as a branch around the
+    // index the compiler's form cost an exec-mask save and restore per pair)
+    uint32_t n1;
+    asm("v_ffbh_i32 %0, %1" : "=v"(n1) : "v"(dw));
+    uint32_t li = (1u << TT::BITS) + (n1 - HD_HUFF_LONG1_N0) * 32u + ((dw << (n1 & 31u)) >> 26);
+    asm("" : "+v"(li));
+    const bool lg = e2 == 0u, eos = n1 >= 30u;
+    HD_CHECK(!(lg & !eos) || li - (1u << TT::BITS) < HD_HUFF_LONG1_ROWS * 32u, 0x207u);
+    di = (lg & !eos) ? li : dw >> (32 - TT::BITS);
+    nG = (lg & eos) ? INT32_MAX : nG;
+  };
   auto pairs = [&](auto dir) {
     constexpr bool kDirect = decltype(dir)::value;
+    if constexpr (LDEF != 0u) {
+      // (LDEF 2: two pairs per trip for the loop's exec-mask bookkeeping
+      // alone; the first takes at most 30 bits)
+      if (LDEF == 2u) {
+        while ((int32_t)nq - 30 >= nG) {
+          pair_def();
+          pair_def();
+        }
+      }
+      while ((int32_t)nq >= nG) pair_def();
+      return;
+    }
     if constexpr (SLOWK == 2u && !kDirect) {
       // SLOWK 2 as two pairs per trip, the second one serving long codes:
       // the slow-code period is static (no counter parity in SALU) and the
@@ -2387,8 +2477,8 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
       if (spec) {
         uint32_t bp = 8u * (s - DD_OV - IBX);
         DiscardSink dk;
-        const DDRun rw = dd_run<DiscardSink, true, false, SK>(S.T, inp, bp, bs, bend, dk, INT32_MAX,
-                                                              dmode, &nslow);
+        const DDRun rw = dd_run<DiscardSink, true, false, SK, C::LDW>(S.T, inp, bp, bs, bend, dk,
+                                                                      INT32_MAX, dmode, &nslow);
         entry = bp;
         dead = rw.failed;
       }
@@ -2401,7 +2491,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
       // same inlined decoder as its re-decodes)
       constexpr bool kMerge = BI == 0;
       if (valid && !dead && !kMerge)
-        rr = dd_run<DISink, false, false, SK>(S.T, inp, bp, bstop, bend, sk, INT32_MAX, dmode, &nslow);
+        rr = dd_run<DISink, false, false, SK, C::LD>(S.T, inp, bp, bstop, bend, sk, INT32_MAX, dmode, &nslow);
       uint32_t my_exit = rr.failed ? XFAIL : bp;
       uint32_t my_entry = dead ? XUNKNOWN : entry;
       uint32_t c0 = sk.count();
@@ -2415,7 +2505,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
           if (run_) {
             DISink s3(my_ob HD_LIM(my_ob + my_rb));
             uint32_t bq = start;
-            rr = dd_run<DISink, false, false, SK>(S.T, inp, bq, bstop, bend, s3, INT32_MAX, dmode, &nslow);
+            rr = dd_run<DISink, false, false, SK, C::LD>(S.T, inp, bq, bstop, bend, s3, INT32_MAX, dmode, &nslow);
             my_exit = rr.failed ? XFAIL : bq;
             c0 = s3.count();
           }
@@ -2440,7 +2530,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
             run_ = true;
           } else {
             uint32_t bq = pred;
-            rr = dd_run<DISink, false, false, SK>(S.T, inp, bq, bstop, bend, s3, INT32_MAX, dmode, &nslow);
+            rr = dd_run<DISink, false, false, SK, C::LD>(S.T, inp, bq, bstop, bend, s3, INT32_MAX, dmode, &nslow);
             my_exit = rr.failed ? XFAIL : bq;
             c0 = s3.count();
           }
