@@ -204,6 +204,260 @@ def test_long_pairs_grid():
         assert sum(1 for c in cases if c[3] is None) == len(BB.LP_PAIRS) * 10
 
 
+# ---- string literals (k_encode<FR>): the grids through BB.literal_rounds ----
+RW_F = K["EC_RW"] + K["EC_RW_F_MARGIN"]
+LONG_F = K["EC_LONG_PAIR_BITS_F"]
+
+
+def lit_views(b):
+    """(tag, string shift, strings, rounds) of a family as built and behind
+    the fill; the model's literal offsets must be the oracle's, and every
+    round must fit k_encode<FR>'s image."""
+    for tag, (pool, off), shift in (("plain", b, 0), ("filled", BB.with_fill(b), BB.FILL_STRINGS)):
+        S = BB.literal_strings(pool, off)
+        assert np.array_equal(S["lo"], O.emit_strings_batch(pool, off)[1]), tag
+        rounds = list(BB.literal_rounds(pool, off))
+        assert max(r["top"] for r in rounds) < RW_F and K["EC_M"] + max(r["nw"] for r in rounds) <= RW_F
+        yield tag, shift, S, rounds
+
+
+def round_of(rounds, t0, q):
+    """The round of wave t0 that holds pool byte q."""
+    return max((r for r in rounds if r["t0"] == t0 and r["base"] <= q), key=lambda r: r["base"])
+
+
+def test_literal_constants():
+    assert LONG_F == 65 and K["EC_RW_F_MARGIN"] == 112 and K["EC_RAW_MASK_BYTES"] == 32
+    assert BB.prefix7_len(np.array([0, 126, 127, 254, 255, 16510, 16511, 2097278, 2097279])).tolist() == \
+        [1, 1, 2, 2, 3, 3, 4, 4, 5]
+    # a 6-byte prefix is out of reach: 2^28 + 127 > NGHTTP2_AMD_ENCODE_MAX_STRING
+    assert BB.PREFIX_EDGES[4] == 2 ** 28 + 127 > 0xFFFFFFFF // 30
+
+
+def test_lit_ties_grid():
+    cases = BB.lit_ties_cases()
+    left_out = sorted(set(BB.ties_plan()) - {(R, B) for R, B, _ in cases})
+    # no such string: fewer than 5 R code bits, or one symbol with no such code
+    assert left_out == [(1, -1), (1, 0), (1, 1), (1, 9), (2, 7), (2, 8), (2, 9)]
+    assert all(B < 5 * R or (R == 1 and B not in BB.LENGTHS) for R, B in left_out)
+    big = [(R, B) for R, B in BB.ties_plan() if R >= 3]
+    assert sum(1 for c in big if c in left_out) <= 0.05 * len(big)
+    for tag, shift, S, rounds in lit_views(BB.lit_ties()):
+        print("lit_ties %s: %d strings (%d of %d planned cases are no string)" % (
+            tag, len(cases), len(left_out), len(BB.ties_plan())))
+        for i, (R, B, huff) in enumerate(cases):
+            k = i + shift
+            assert (S["R"][k], S["bits"][k], bool(S["H"][k])) == (R, B, huff), (R, B)
+            assert S["P"][k] == (R - 1 if huff else R)
+        assert cases[0] == (0, 0, False) and S["PL"][shift] == 1 and S["P"][shift] == 0
+        assert not any(h for R, _, h in cases if R <= 1)
+        for R in BB.TIE_R[2:]:  # both sides, and the tie itself (E = R stays raw)
+            got = {B - 8 * (R - 1): h for r, B, h in cases if r == R}
+            assert got == {-1: True, 0: True, 1: False, 7: False, 8: False, 9: False}, R
+        assert {B - 8 for R, B, h in cases if R == 2} == {7, 8, 9}
+
+
+def test_lit_prefix_grid():
+    cases = BB.lit_prefix_cases()
+    want = {126: 1, 127: 2, 254: 2, 255: 3, 16510: 3, 16511: 4, 2097278: 4, 2097279: 5}
+    for tag, shift, S, rounds in lit_views(BB.lit_prefix()):
+        print("lit_prefix %s: %d strings, %d bytes" % (tag, len(S["R"]) - shift, int(S["off"][-1])))
+        align = {}
+        for i, P, kind, lead in cases:
+            k = i + shift
+            assert S["P"][k] == P and S["PL"][k] == want[P] and bool(S["H"][k]) == (kind == "huff")
+            assert (S["R"][k] == P) == (kind == "raw")
+            align.setdefault((P, kind), set()).add(int(S["lo"][k]) % 4)
+        assert set(align) == {(P, kind) for P in want for kind in ("raw", "huff")}
+        assert all(a == {0, 1, 2, 3} for (P, _), a in align.items() if P < 2 ** 20)
+        assert set().union(*(a for (P, _), a in align.items() if P >= 2 ** 20)) == {0, 1, 2, 3}
+        assert {c[3] for c in cases} == {0, 1, 2, 3}  # leads of 0..3 output bytes
+    small = BB.lit_prefix(big=False)
+    assert int(small[1][-1]) < 400000 and len(BB.lit_prefix_cases(big=False)) == len(cases) - 4
+
+
+def test_lit_raw_spans_grid():
+    cases = BB.lit_raw_spans_cases()
+    W = K["EC_RAW_MASK_BYTES"]
+    for tag, shift, S, rounds in lit_views(BB.lit_raw_spans()):
+        print("lit_raw_spans %s: %d strings, %d bytes" % (tag, len(S["R"]) - shift, int(S["off"][-1])))
+        off = S["off"]
+        seen, full_words, crossing = set(), {}, 0
+        for i, ln, o, modulus in cases:
+            k = i + shift
+            A16 = int(off[k - k % 64]) & ~15
+            a, b = int(off[k]) - A16, int(off[k + 1]) - A16
+            assert k % 64 and (a % modulus, b - a, bool(S["H"][k])) == (o, ln, False)
+            assert S["H"][k - 1] and S["H"][k + 1] and S["R"][k - 1] >= 2  # coded bytes on both sides
+            seen.add((ln, a % W))
+            full_words.setdefault(ln, set()).add(b // W - -(-a // W) if b // W > -(-a // W) else 0)
+            crossing += a // K["EC_ROUND_BYTES"] != (b - 1) // K["EC_ROUND_BYTES"]
+        assert seen >= {(ln, o) for ln in BB.SPAN_LENS for o in range(W)}
+        assert full_words[31] == {0} and full_words[32] == {0, 1} and 1 in full_words[33] and \
+            full_words[64] == {1, 2} and max(full_words[1056]) == 33
+        assert crossing >= 32
+        order = set()
+        for r in rounds:
+            inw = (r["base"] + np.arange(len(r["raw"])) < r["Z"]) & (r["bits"] > 0)
+            ev, od = r["raw"][0::2], r["raw"][1::2]
+            both = inw[0::2] & inw[1::2]
+            order |= {"raw,coded"} if (both & ev & ~od).any() else set()
+            order |= {"coded,raw"} if (both & ~ev & od).any() else set()
+            if len(r["raw"]) == K["EC_ROUND_BYTES"] and r["raw"].all():
+                order.add("full round")
+            if r["raw"].size % W == 0 and r["raw"].reshape(-1, W).all(axis=1).any():
+                order.add("full word")
+        assert order == {"raw,coded", "coded,raw", "full round", "full word"}
+
+
+def test_lit_empties_grid():
+    cases = BB.lit_empties_cases()
+    for tag, shift, S, rounds in lit_views(BB.lit_empties()):
+        print("lit_empties %s: %d strings, %d bytes, %d bytewise rounds" % (
+            tag, len(S["R"]) - shift, int(S["off"][-1]), sum(r["bytewise"] for r in rounds)))
+        off, last = S["off"], BB.LEN[S["raw"]]
+        ext = {}
+        for r in rounds:
+            for j in np.nonzero(r["extras"])[0]:
+                ext[r["base"] + int(j)] = int(r["extras"][j])
+        hit = set()
+        for where, kind, k, first in cases:
+            f = first + shift
+            assert (S["R"][f:f + k] == 0).all() and (where == "start" or S["R"][f - 1] > 0)
+            if where == "start":
+                assert f % 64 == 0 and S["R"][f + k] > 0
+            if where == "whole":
+                assert f % 64 == 0 and k % 64 == 0
+            if where == "end":
+                assert (f + k) % 64 == 0
+            if where in ("run", "end"):  # the byte before the run, by kind
+                q = int(off[f]) - 1
+                if kind == "raw":
+                    assert not S["H"][f - 1]
+                else:
+                    assert S["H"][f - 1] and last[q] == (5 if kind == "h5" else 30)
+                if f % 64:  # the pad, the run's prefixes and the next string's, up to the wave's end
+                    here = np.arange(f, min(f + k + 1, f - f % 64 + 64))
+                    assert (off[here] == q + 1).all()
+                    assert ext[q] == int(S["pad"][f - 1]) + 8 * int(S["PL"][here].sum()), (where, kind, k)
+                    hit.add((kind, k, q % 2))
+        assert hit >= {(kind, k, p) for kind in BB.EMPTY_BEHIND for k in range(1, 10) for p in (0, 1)}
+        assert {k for w, _, k, _ in cases if w == "run"} == set(BB.EMPTY_RUNS)
+        waves = {}
+        for r in rounds:
+            if r["first"]:
+                waves[r["t0"]] = r
+        assert {r["A"] & 15 for r in waves.values() if r["whole_empty"]} == {0}
+        assert sum(r["whole_empty"] for r in waves.values()) >= 6  # c_end == c0
+        assert {r["A"] & 15 for r in waves.values() if r["A"] == r["Z"]} >= {0, 1, 15}
+        assert {(r["A"] & 15, r["at_a"]) for r in waves.values() if r["Z"] > r["A"]} >= {
+            (a, k + 1) for a in (0, 1, 15) for k in (1, 3, 63)} | {(a, 1) for a in (0, 1, 15)}
+        assert any(r["bytewise"] for r in rounds) and any(not r["bytewise"] for r in rounds)
+    for n in BB.ALL_EMPTY_N:
+        pool, off = BB.lit_all_empty(n)
+        assert pool.size == 0 and len(off) == n + 1
+        rounds = list(BB.literal_rounds(pool, off))
+        assert len(rounds) == -(-n // 64) and all(r["whole_empty"] and r["XS"] == 8 * r["at_a"] for r in rounds)
+
+
+def test_lit_pairs64_grid():
+    cases = BB.lit_pairs64_cases()
+    for tag, shift, S, rounds in lit_views(BB.lit_pairs64()):
+        print("lit_pairs64 %s: %d strings, %d bytes, %d bytewise rounds of %d" % (
+            tag, len(S["R"]) - shift, int(S["off"][-1]), sum(r["bytewise"] for r in rounds), len(rounds)))
+        fo = int(S["off"][shift])
+        found, short = set(), set()
+        for what, T, chunk, slot, PL, first, q, (l0, pad, e, l1) in cases:
+            k, q = first + shift, q + fo
+            r = round_of(rounds, k - k % 64, q)
+            at = q - r["base"]
+            assert at % 2 == 0 and S["H"][k] and S["pad"][k] == pad and S["PL"][k + e + 1] == PL
+            assert (S["R"][k + 1:k + e + 1] == 0).all() and S["H"][k + e + 1]
+            j = at >> 1
+            assert r["L0"][j] == l0 + pad + 8 * (e + PL) and r["pairs"][j] == r["L0"][j] + l1
+            assert (r["pairs"][j] if what == "sum" else r["L0"][j]) == T
+            if chunk is None:
+                short.add((what, T))
+                continue
+            assert (r["round"], at >> 4, (at & 15) >> 1) == (1, chunk, slot) and not r["first"]
+            # the only long pair of its round: the round's path is this pair's
+            assert r["pairs"].max() == r["pairs"][j] and (r["pairs"] >= 61).sum() == 1
+            assert r["bytewise"] == (r["pairs"][j] >= LONG_F)
+            found.add((what, T, chunk, slot, PL))
+        assert found == {(w, T, c, s, PL) for w, T in BB.P64_TARGETS for c in BB.P64_CHUNKS
+                         for s in BB.P64_SLOTS for PL in (1, 2, 3)}
+        assert short == set(BB.P64_TARGETS)
+        assert {T for w, T in BB.P64_TARGETS if w == "sum"} == {LONG_F - 2, LONG_F - 1, LONG_F, 72}
+        assert {T for w, T in BB.P64_TARGETS if w == "L0"} == {64, 69, 128}
+
+
+def test_lit_round_edges_grid():
+    cases = BB.lit_round_edges_cases()
+    RB = K["EC_ROUND_BYTES"]
+    assert BB.EDGE_AT == (RB - 1, RB, RB + 1, 2 * RB - 1, 2 * RB, 2 * RB + 1)
+    for tag, shift, S, rounds in lit_views(BB.lit_round_edges()):
+        print("lit_round_edges %s: %d strings, %d bytes" % (tag, len(S["R"]) - shift, int(S["off"][-1])))
+        off = S["off"]
+        align = {}
+        for i, at, PL, kind, lead in cases:
+            k = i + shift
+            A = int(off[k - k % 64])
+            assert A % 16 == 0 and int(off[k]) - A == at and S["PL"][k] == PL
+            assert bool(S["H"][k]) == (kind == "huff") and S["H"][k - 1]
+            r = round_of(rounds, k - k % 64, A + at - 1)  # the prefix: extras of the byte before
+            assert r["round"] == (at - 1) // RB
+            assert r["extras"][(at - 1) % RB] == int(S["pad"][k - 1]) + 8 * PL
+            align.setdefault((at, PL, kind), set()).add(int(S["lo"][k]) % 4)
+        assert len(align) == 36 and all(a == {0, 1, 2, 3} for a in align.values())
+
+
+def test_lit_dense_round_grid():
+    for tag, shift, S, rounds in lit_views(BB.lit_dense_round()):
+        k = shift + 31
+        assert len(S["R"]) - shift == 64 and S["H"][k] and S["R"][k] == BB.DENSE_FIVES + BB.DENSE_LONG
+        assert (np.delete(S["R"][shift:], 31) == 1).all()
+        dense = [r for r in rounds if len(r["bits"]) == K["EC_ROUND_BYTES"] and (r["bits"] == 30).all()]
+        assert len(dense) == 1 and not dense[0]["first"] and not dense[0]["last"]
+        assert dense[0]["nw"] >= 30 * K["EC_ROUND_BYTES"] // 32 and not dense[0]["bytewise"]
+        print("lit_dense_round %s: a round of %d words, image top %d of %d" % (
+            tag, dense[0]["nw"], max(r["top"] for r in rounds), RW_F))
+
+
+def test_no_index_fields_literal_batch():
+    """The deflater's literal batch for no_index_fields() is what
+    no_index_literals() says (each literal, framed, in the oracle deflater's
+    wire in that order, and nothing but representation bytes between), and
+    it has a pair of more than 64 bits: the bytewise path, from the wire."""
+    from oracle import hpack_oracle as HO
+    assert BB.NO_INDEX == HO.NO_INDEX
+    fields = BB.no_index_fields()
+    wire = HO.Deflater().deflate_block(fields)
+    st, got = HO.Inflater().inflate_block(wire)
+    assert [(n, v) for n, v, _ in got] == [(n, v) for n, v, _ in fields]
+    assert [f for _, _, f in got] == [f for _, _, f in fields]
+    pool, off = BB.no_index_literals()
+    lit, lo = O.emit_strings_batch(pool, off)
+    at, between = 0, 0
+    for i in range(len(off) - 1):
+        k = wire.find(bytes(lit[lo[i]:lo[i + 1]]), at)
+        assert k >= at
+        between += k - at
+        at = k + int(lo[i + 1] - lo[i])
+    # representation bytes: 40 for a new name, 1f xx for a static index >= 15 never indexed
+    assert at == len(wire) and between == 2 + 2 * len(BB.NO_INDEX_NAMES)
+    rounds = list(BB.literal_rounds(pool, off))
+    assert len(rounds) == 1 and rounds[0]["bytewise"]
+    assert rounds[0]["pairs"].max() >= 8 * len(BB.NO_INDEX_NAMES) + 5 >= LONG_F
+
+
+def test_tile_chunks():
+    b = BB.lit_raw_spans()
+    parts = list(BB.tile_chunks(b))
+    assert all(len(o) - 1 <= 256 and int(o[0]) == 0 for _, o in parts)
+    assert b"".join(bytes(p) for p, _ in parts) == bytes(b[0])
+    assert sum(len(o) - 1 for _, o in parts) == len(b[1]) - 1
+
+
 def test_with_fill_keeps_alignment():
     pool, off = BB.with_fill(BB.long_pairs())
     assert int(off[BB.FILL_STRINGS]) % 16 == 0 and BB.FILL_STRINGS == 256

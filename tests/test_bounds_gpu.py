@@ -7,7 +7,7 @@ cases of tests/test_parity_gpu.py through it -- encode, both decode_batch_auto
 instances, the slot decoder, emit_strings, adversarial and window-edge
 inputs, NGHTTP2_HD_MAX_NV-sized and empty strings, one-tile batches, and the
 boundary grids of tests/boundary_batches.py (straddle, ends, tasks,
-round_words, long_pairs) -- and after each asks nghttp2_amd_hd__bounds_check for the first recorded
+round_words, long_pairs and the seven string-literal families) -- and after each asks nghttp2_amd_hd__bounds_check for the first recorded
 violation, which must be none.  The report path itself is checked by the
 build's self-test kernel (site 0x1FF)."""
 import ctypes
@@ -92,7 +92,11 @@ for tag, (enc, eoff) in (("straddle", BB.straddle()), ("ends", BB.ends()), ("tas
     for pick in ("items64", "pieces40"):
         T.auto_decode_check(codec, dev, enc, eoff, tag + " " + pick, pick=pick)
     done(tag)
-for tag, (pool, off) in (("round_words", BB.round_words()), ("long_pairs", BB.long_pairs())):
+# ... and the string-literal grids (k_encode<FR>: sites 0x101-0x105; lit_prefix without its 2 MB strings)
+LIT = [(f, BB.lit_prefix(big=False) if f == "lit_prefix" else getattr(BB, f)()) for f in BB.LIT_FAMILIES]
+LIT += [(f + " filled", BB.with_fill(b)) for f, b in LIT if f in ("lit_dense_round", "lit_empties", "lit_pairs64")]
+LIT += [("all-empty n=%%d" %% n, BB.lit_all_empty(n)) for n in BB.ALL_EMPTY_N]
+for tag, (pool, off) in [("round_words", BB.round_words()), ("long_pairs", BB.long_pairs())] + LIT:
     T.check_roundtrip(codec, dev, pool, off, tag)
     enc, eoff = O.encode_batch(pool, off)
     for pick in ("items64", "pieces40"):
