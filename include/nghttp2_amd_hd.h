@@ -335,10 +335,11 @@ NGHTTP2_AMD_EXTERN uint32_t nghttp2_amd_hd_name_hash(const uint8_t *name, size_t
  * the result is a uint8 mask, a bit set exactly when the reference function
  * returns 1 for the string.
  *
- * Out of scope: nghttp2_check_nonempty_header_name's 0-versus-2 result for a
- * refused name (it depends on which bad byte comes first; NAME_LOWER only
- * says whether it returns 1), and the authority table without '@' that is
- * private to lib/nghttp2_http.c (AUTHORITY is the public
+ * NAME_LOWER says whether nghttp2_check_nonempty_header_name returns 1; its
+ * 0-versus-2 result for a refused name (which bad byte comes first) is told
+ * apart by nghttp2_amd_hd_http_on_header below, and the authority table
+ * without '@' that is private to lib/nghttp2_http.c is
+ * NGHTTP2_AMD_HTTP_FACT_AUTHORITY (AUTHORITY here is the public
  * nghttp2_check_authority, which allows '@').
  */
 #define NGHTTP2_AMD_CHECK_NAME 0x01u          /* nghttp2_check_header_name: empty 0, a leading ':' skipped, ":" 0 */
@@ -370,6 +371,135 @@ NGHTTP2_AMD_EXTERN uint8_t nghttp2_amd_hd_check_field(const uint8_t *s, size_t l
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_check_fields_batch(const uint8_t *pool, const uint32_t *off,
                                                          const int32_t *len, uint32_t n, uint8_t *mask,
                                                          void *stream);
+
+/* ------------------------------------------------------------------ */
+/* HTTP message validation (nghttp2_http_on_header)                     */
+/* ------------------------------------------------------------------ */
+/*
+ * Replaces nghttp2_http_on_header (lib/nghttp2_http.c:405-447, called from
+ * lib/nghttp2_session.c:3588 on every field an inflater hands over) and the
+ * two block-end functions (:449-511).  The reference function switches on
+ * nv.token, runs byte checks on the value and keeps the stream's http_flags,
+ * content_length and status_code.  Here the byte work is split off: the
+ * NGHTTP2_AMD_CHECK_* masks above, the name token, and the value facts below
+ * are computed once per string (on the GPU for a batch), and the per-field
+ * step is a pure host function of those that reads no value byte.
+ *
+ * Value facts: one uint32 per string, a bit set exactly when the reference's
+ * test passes for the string, and one int64, parse_uint's value.
+ * parse_status_code (:56-63) needs no bytes beyond them: it is UINT && len
+ * == 3 && number >= 100; the "0" test of :357 is len == 1 && number == 0.
+ */
+#define NGHTTP2_AMD_HTTP_FACT_AUTHORITY 0x001u     /* check_authority (:168-176): no '@'; empty 1 */
+#define NGHTTP2_AMD_HTTP_FACT_SCHEME 0x002u        /* check_scheme (:118-140): empty 0 */
+#define NGHTTP2_AMD_HTTP_FACT_SCHEME_HTTP 0x004u   /* memieq against "http" / "https" (:246-247) */
+#define NGHTTP2_AMD_HTTP_FACT_METH_HEAD 0x008u     /* exactly "HEAD" (:204-228) */
+#define NGHTTP2_AMD_HTTP_FACT_METH_CONNECT 0x010u  /* exactly "CONNECT" */
+#define NGHTTP2_AMD_HTTP_FACT_METH_OPTIONS 0x020u  /* exactly "OPTIONS" */
+#define NGHTTP2_AMD_HTTP_FACT_PATH_SLASH 0x040u    /* not empty, first byte '/' */
+#define NGHTTP2_AMD_HTTP_FACT_PATH_ASTERISK 0x080u /* exactly "*" */
+#define NGHTTP2_AMD_HTTP_FACT_TE_TRAILERS 0x100u   /* lstrieq("trailers", ...) */
+#define NGHTTP2_AMD_HTTP_FACT_LWS 0x200u           /* lws() (:142-150): SP / HT only; empty 1 */
+#define NGHTTP2_AMD_HTTP_FACT_UINT 0x400u          /* parse_uint (:65-89) does not return -1 */
+#define NGHTTP2_AMD_HTTP_FACT_INVALID 0x80000000u  /* the string was not examined; every other bit is 0 */
+
+/* The facts of one host string (no GPU); *number (may be NULL) = parse_uint's
+ * value when UINT is set, else -1. */
+NGHTTP2_AMD_EXTERN uint32_t nghttp2_amd_hd_http_facts(const uint8_t *s, size_t len, int64_t *number);
+
+/*
+ * The facts of N strings: facts[i] and number[i] (OUT, n entries each) for
+ * string i, in exactly the layouts nghttp2_amd_hd_check_fields_batch takes
+ * (len == NULL or given; a decode's (dst, dst_off, status) as is; the pool
+ * 16-byte aligned and readable to align_up(off[n], 16) + 16).  A string gets
+ * NGHTTP2_AMD_HTTP_FACT_INVALID and number -1, and none of its bytes is
+ * read, when len[i] < 0, off[i] + len[i] > off[i+1] or off[i] > off[i+1].
+ * Bytes outside a string never influence its facts.  Exact for a string of
+ * any length: parse_uint accepts any number of leading zeros and refuses at
+ * the first overflow past INT64_MAX.  Device pointers, asynchronous on
+ * `stream`; n == 0 returns 0, a NULL pool, off, facts or number
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_http_facts_batch(const uint8_t *pool, const uint32_t *off,
+                                                       const int32_t *len, uint32_t n, uint32_t *facts,
+                                                       int64_t *number, void *stream);
+
+/* The stream's HTTP state the reference keeps in nghttp2_stream; a fresh
+ * stream is {0, -1, -1}.  http_flags are NGHTTP2_HTTP_FLAG_* of
+ * lib/nghttp2_stream.h:99-138. */
+typedef struct {
+  uint32_t http_flags;
+  int32_t status_code;
+  int64_t content_length;
+} nghttp2_amd_hd_http_state;
+
+#define NGHTTP2_AMD_HTTP_FLAG__AUTHORITY 0x01u
+#define NGHTTP2_AMD_HTTP_FLAG__PATH 0x02u
+#define NGHTTP2_AMD_HTTP_FLAG__METHOD 0x04u
+#define NGHTTP2_AMD_HTTP_FLAG__SCHEME 0x08u
+#define NGHTTP2_AMD_HTTP_FLAG_HOST 0x10u
+#define NGHTTP2_AMD_HTTP_FLAG__STATUS 0x20u
+#define NGHTTP2_AMD_HTTP_FLAG_REQ_HEADERS \
+  (NGHTTP2_AMD_HTTP_FLAG__METHOD | NGHTTP2_AMD_HTTP_FLAG__PATH | NGHTTP2_AMD_HTTP_FLAG__SCHEME)
+#define NGHTTP2_AMD_HTTP_FLAG_PSEUDO_HEADER_DISALLOWED 0x40u
+#define NGHTTP2_AMD_HTTP_FLAG_METH_CONNECT 0x80u
+#define NGHTTP2_AMD_HTTP_FLAG_METH_HEAD 0x0100u
+#define NGHTTP2_AMD_HTTP_FLAG_METH_OPTIONS 0x0200u
+#define NGHTTP2_AMD_HTTP_FLAG_METH_UPGRADE_WORKAROUND 0x0400u
+#define NGHTTP2_AMD_HTTP_FLAG_METH_ALL                                           \
+  (NGHTTP2_AMD_HTTP_FLAG_METH_CONNECT | NGHTTP2_AMD_HTTP_FLAG_METH_HEAD |        \
+   NGHTTP2_AMD_HTTP_FLAG_METH_OPTIONS | NGHTTP2_AMD_HTTP_FLAG_METH_UPGRADE_WORKAROUND)
+#define NGHTTP2_AMD_HTTP_FLAG_PATH_REGULAR 0x0800u
+#define NGHTTP2_AMD_HTTP_FLAG_PATH_ASTERISK 0x1000u
+#define NGHTTP2_AMD_HTTP_FLAG_SCHEME_HTTP 0x2000u
+#define NGHTTP2_AMD_HTTP_FLAG_EXPECT_FINAL_RESPONSE 0x4000u
+#define NGHTTP2_AMD_HTTP_FLAG__PROTOCOL 0x8000u
+#define NGHTTP2_AMD_HTTP_FLAG_PRIORITY 0x010000u /* left to the caller, see below */
+#define NGHTTP2_AMD_HTTP_FLAG_BAD_PRIORITY 0x020000u
+
+/* What the reference reads from the session, the frame and the stream id. */
+#define NGHTTP2_AMD_HTTP_MODE_REQUEST 0x01u          /* session->server or a PUSH_PROMISE; clear: a response */
+#define NGHTTP2_AMD_HTTP_MODE_PUSH 0x02u             /* even stream id: CONNECT refused, priority not parsed */
+#define NGHTTP2_AMD_HTTP_MODE_TRAILER 0x04u          /* the block is a trailer */
+#define NGHTTP2_AMD_HTTP_MODE_CONNECT_PROTOCOL 0x08u /* the extended CONNECT setting is enabled */
+#define NGHTTP2_AMD_HTTP_MODE_NO_RFC9113_WS 0x10u    /* RFC 9113's leading/trailing whitespace rule is off */
+
+#define NGHTTP2_AMD_ERR_IGN_HTTP_HEADER (-105)    /* nghttp2.h NGHTTP2_ERR_IGN_HTTP_HEADER */
+#define NGHTTP2_AMD_ERR_REMOVE_HTTP_HEADER (-106) /* NGHTTP2_ERR_REMOVE_HTTP_HEADER */
+#define NGHTTP2_AMD_ERR_HTTP_HEADER (-531)        /* NGHTTP2_ERR_HTTP_HEADER */
+#define NGHTTP2_AMD_ERR_HTTP_MESSAGING (-532)     /* NGHTTP2_ERR_HTTP_MESSAGING */
+
+/*
+ * nghttp2_http_on_header for one field, from what the batch calls computed:
+ * the name's token and NGHTTP2_AMD_CHECK_* mask, and the value's mask, facts
+ * and number.  Returns 0, NGHTTP2_AMD_ERR_IGN_HTTP_HEADER,
+ * NGHTTP2_AMD_ERR_REMOVE_HTTP_HEADER or NGHTTP2_AMD_ERR_HTTP_HEADER and
+ * updates *state exactly as lib/nghttp2_http.c:188-447 does.  It reads no
+ * value byte; of the name it reads the first byte, and the rest only when
+ * NAME_LOWER is clear, to tell nghttp2_check_nonempty_header_name's 0 from
+ * its 2 (lib/nghttp2_helper.c:380-392).  A NULL state is
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT (from the two block-end functions too); a
+ * NULL name is an empty one.
+ *
+ * Out of scope: the `priority` field's structured value
+ * (nghttp2_http_parse_priority) is not parsed.  The verdict does not depend
+ * on the parse and stays exact; BAD_PRIORITY is set when the value check
+ * fails; NGHTTP2_AMD_HTTP_FLAG_PRIORITY, BAD_PRIORITY after a failed parse
+ * and http_extpri are left to the caller.  nghttp2_http_on_trailer_headers,
+ * _on_remote_end_stream, _on_data_chunk and _record_request_method read
+ * frame flags and DATA, not header fields, and are left out.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_http_on_header(nghttp2_amd_hd_http_state *state, uint32_t mode,
+                                                     const uint8_t *name, size_t name_len,
+                                                     size_t value_len, int32_t token, uint8_t name_mask,
+                                                     uint8_t value_mask, uint32_t value_facts,
+                                                     int64_t value_number);
+/* nghttp2_http_on_request_headers (:449-484; mode's PUSH bit stands for the
+ * PUSH_PROMISE frame type) and nghttp2_http_on_response_headers (:486-511):
+ * 0 or -1. */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_http_on_request_headers(nghttp2_amd_hd_http_state *state,
+                                                              uint32_t mode);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_http_on_response_headers(nghttp2_amd_hd_http_state *state);
 
 /* ------------------------------------------------------------------ */
 /* Batched HPACK inflate front-end               */
@@ -483,6 +613,52 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_infla
                                   size_t nva_cap, size_t *nva_used, uint8_t *arena,
                                   size_t arena_cap, size_t *arena_used, int32_t *block_status,
                                   uint8_t *nv_checks, int32_t *nv_tokens, void *stream);
+
+/*
+ * nghttp2_amd_hd_inflate_blocks_fields that also validates the HTTP message
+ * each block carries, as the session does with nghttp2_http_on_header on
+ * every field and a block-end function after the last (see "HTTP message
+ * validation" above).  block_modes[i] (IN) is block i's
+ * NGHTTP2_AMD_HTTP_MODE_* bits.  block_state[i] is IN-OUT: the caller puts in
+ * the stream's state before the block (fresh, {0, -1, -1}, for a request; the
+ * request's method flags for a response; what a 1xx block left behind for
+ * the response after it) and the state after the block comes out.
+ * nv_verdicts[k] (nva_cap entries, the first *nva_used written) is
+ * nghttp2_amd_hd_http_on_header's result for field k, run in order on the
+ * block's state.  After the first NGHTTP2_AMD_ERR_HTTP_HEADER of a block the
+ * reference stops examining the stream (lib/nghttp2_session.c:3643-3664): the
+ * block's later fields get NGHTTP2_AMD_HTTP_NOT_EXAMINED and the state stops
+ * changing; those fields are still emitted and still enter the dynamic table.
+ * block_http[i] is NGHTTP2_AMD_ERR_HTTP_HEADER if a field failed, else
+ * NGHTTP2_AMD_ERR_HTTP_MESSAGING if the block-end function of the mode
+ * (request or response; none for a TRAILER block) returns -1, else 0.  For a
+ * block whose block_status is NGHTTP2_AMD_ERR_HEADER_COMP the fields emitted
+ * before the error get verdicts and block_http[i] is
+ * NGHTTP2_AMD_ERR_HEADER_COMP; a block cut off by
+ * NGHTTP2_AMD_ERR_BUFFER_ERROR leaves its state untouched and gets that code
+ * in block_http too.
+ * The value facts come from where the masks and tokens come from: Huffman
+ * literals from one nghttp2_amd_hd_http_facts_batch over the decode's output
+ * (one more launch behind the check and token launches, twelve bytes per
+ * literal more in the copy back), raw literals on the replay's thread,
+ * static-table entries once per process; a dynamic-table entry carries its
+ * value's facts from insertion, or from its first reference by an _http call
+ * when another kind of call inserted it.  The call computes masks and tokens
+ * internally whether or not nv_checks and nv_tokens are given.  nv_verdicts
+ * and block_http may be NULL; block_modes and block_state are both needed
+ * (else NGHTTP2_AMD_ERR_INVALID_ARGUMENT) unless all four are NULL, which is
+ * nghttp2_amd_hd_inflate_blocks_fields itself: no launch, no byte more in
+ * the copies, no host work.
+ */
+#define NGHTTP2_AMD_HTTP_NOT_EXAMINED 1
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflater *const *inflaters,
+                                  uint32_t nblocks, const uint8_t *const *blocks,
+                                  const size_t *block_lens, nghttp2_amd_hd_nv *nva,
+                                  size_t nva_cap, size_t *nva_used, uint8_t *arena,
+                                  size_t arena_cap, size_t *arena_used, int32_t *block_status,
+                                  uint8_t *nv_checks, int32_t *nv_tokens,
+                                  const uint8_t *block_modes, nghttp2_amd_hd_http_state *block_state,
+                                  int32_t *nv_verdicts, int32_t *block_http, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* Batched HPACK deflate front-end                                      */

@@ -30,6 +30,7 @@
 #include "../../include/nghttp2_amd_hd.h"
 #include "hd_field_classes.h"
 #include "hd_host.h"
+#include "hd_http.h"
 #include "hd_tokens.h"
 #include "host_threads.h"
 
@@ -51,15 +52,19 @@ const uint32_t kDefaultTable = 4096;   // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
 // (kUnchecked until a checked call computes them: at insertion, or at the
 // first reference to an entry that an unchecked call inserted), so an indexed
 // field costs a checked call no byte scan.  The name's token (lookup_token)
-// travels the same way: kTokUnknown until a tokened call sets it.
+// travels the same way: kTokUnknown until a tokened call sets it, and so do the
+// value's HTTP facts and number (hd_http.h): kFactUnknown until an _http call.
 const uint8_t kUnchecked = NGHTTP2_AMD_CHECK_INVALID;
 const int8_t kTokUnknown = -3;  // (below NGHTTP2_AMD_TOKEN_INVALID; a token is -1..67)
+const uint32_t kFactUnknown = NGHTTP2_AMD_HTTP_FACT_INVALID;
 struct DynTable {
   struct Ent {
     size_t off;
     uint32_t nl, vl;
     uint8_t cn = kUnchecked, cv = kUnchecked;
     int8_t tk = kTokUnknown;
+    uint32_t vf = kFactUnknown;  // the value's facts and number
+    int64_t vn = -1;
   };
   std::vector<Ent> ents;   // ring, capacity a power of two
   size_t e_first = 0;      // oldest entry
@@ -106,7 +111,8 @@ struct DynTable {
     buf.swap(nb);
   }
   // n / v must not point into this table (the caller passes copies)
-  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk) {
+  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk,
+            uint32_t vf, int64_t vn) {
     if (count == ents.size()) {  // grow the descriptor ring, oldest first
       std::vector<Ent> ne(ents.empty() ? 16 : 2 * ents.size());
       for (size_t k = 0; k < count; ++k) ne[k] = ents[(e_first + k) & (ents.size() - 1)];
@@ -120,7 +126,7 @@ struct DynTable {
     }
     if (nl) memcpy(buf.data() + at, n, nl);
     if (vl) memcpy(buf.data() + at + nl, v, vl);
-    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, cn, cv, tk};
+    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, cn, cv, tk, vf, vn};
     ++count;
   }
 };
@@ -151,12 +157,14 @@ struct nghttp2_amd_hd_inflater {
   // outside the table (the caller's emitted field), so a name taken from an
   // entry that this insertion evicts stays valid, as in the reference.
   // cn / cv: the field's check masks (kUnchecked from an unchecked call);
-  // tk: its name's token (kTokUnknown from a call without tokens).
-  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk) {
+  // tk: its name's token (kTokUnknown from a call without tokens); vf / vn:
+  // its value's HTTP facts (kFactUnknown from a call that is not _http).
+  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk,
+           uint32_t vf, int64_t vn) {
     const size_t room = nl + vl + kEntryOverhead;
     while (bufsize + room > bufsize_max && table.count) evict_oldest();
     if (room > bufsize_max) return;
-    table.push(n, nl, v, vl, cn, cv, tk);
+    table.push(n, nl, v, vl, cn, cv, tk, vf, vn);
     bufsize += room;
     max_nl = std::max(max_nl, nl);
     max_vl = std::max(max_vl, vl);
@@ -215,6 +223,28 @@ struct nghttp2_amd_hd_inflater {
     if (e.tk == kTokUnknown) e.tk = (int8_t)hdtok::lookup_token(table.name(e), e.nl);
     return e.tk;
   }
+  // the HTTP facts and number of entry idx's value (as entry()), from the same
+  // two places
+  uint32_t entry_facts(size_t idx, int64_t *vn) {
+    if (idx < kStaticLen) {
+      struct Facts {
+        uint32_t f[kStaticLen];
+        int64_t n[kStaticLen];
+      };
+      static const Facts st = [] {
+        Facts t;
+        for (uint32_t i = 0; i < kStaticLen; ++i)
+          t.f[i] = hdhttp::http_facts((const uint8_t *)kStatic[i][1], kStaticLens.len[i][1], &t.n[i]);
+        return t;
+      }();
+      *vn = st.n[idx];
+      return st.f[idx];
+    }
+    DynTable::Ent &e = table.newest(idx - kStaticLen);
+    if (e.vf == kFactUnknown) e.vf = hdhttp::http_facts(table.value(e), e.vl, &e.vn);
+    *vn = e.vn;
+    return e.vf;
+  }
 };
 
 namespace {
@@ -264,6 +294,7 @@ struct Rec {
   uint8_t flags;
   uint8_t cn, cv;  // the check masks of name and value (a checked call)
   int8_t tk;       // the name's token (a tokened call)
+  int32_t vd;      // the field's HTTP verdict (an _http call)
 };
 // A growable byte buffer written through a raw pointer (no per-append
 // capacity check or zero fill): a block's name\0value\0 runs.
@@ -294,13 +325,15 @@ struct alignas(128) BlockOut {
   std::vector<Rec> recs;
   ByteBuf bytes;
   int32_t status = 0;
+  nghttp2_amd_hd_http_state hst{};  // an _http call: the state after the block, and the block's result
+  int32_t hres = 0;
 };
 
 struct Engine {
   std::mutex mu;
   PinnedBuf h_pool;  // Huffman literals in
   PinnedBuf h_out;   // decoded literals out
-  PinnedBuf h_meta;  // uint32: offsets in, then slots and status out ((nh + 1) each), tokens, masks
+  PinnedBuf h_meta;  // uint32: offsets in, then slots and status out ((nh + 1) each), facts, tokens, masks
   DevBuf d_in, d_out, d_meta;  // their device copies (the modes that copy)
   std::vector<BlockOut> outs;
   // pass 1 state, kept across calls (under mu)
@@ -369,6 +402,8 @@ struct LitSrc {
   const int32_t *st;
   const uint8_t *chk;  // a checked call: the decoded literals' check masks (the GPU's)
   const int32_t *tok;  // a tokened call: the decoded literals' tokens (the GPU's)
+  const uint32_t *fct;  // an _http call: the decoded literals' HTTP facts and numbers (the GPU's)
+  const int64_t *num;
   // false: -523 (bad padding or EOS, hd_inflate_read_huff :1740-1750)
   bool get(const Lit &l, const char **p, size_t *n) const {
     if (l.huff < 0) {
@@ -388,6 +423,12 @@ struct LitSrc {
   // the token of a name literal get() returned, from the same two places
   int8_t token(const Lit &l) const {
     return (int8_t)(l.huff < 0 ? hdtok::lookup_token(l.p, l.len) : tok[l.huff]);
+  }
+  // the HTTP facts and number of a value literal get() returned, likewise
+  uint32_t facts(const Lit &l, int64_t *vn) const {
+    if (l.huff < 0) return hdhttp::http_facts(l.p, l.len, vn);
+    *vn = num[l.huff];
+    return fct[l.huff];
   }
 };
 
@@ -426,9 +467,11 @@ struct BlockSink {
     out.recs.clear();
     out.bytes.clear();
   }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk) {
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk,
+            int32_t vd) {
     Rec r;
     r.flags = flags;
+    r.vd = vd;
     r.cn = cn;
     r.cv = cv;
     r.tk = tk;
@@ -455,10 +498,13 @@ struct DirectSink {
   int32_t *status;
   uint8_t *checks;  // the caller's nv_checks, or nullptr
   int32_t *tokens;  // the caller's nv_tokens, or nullptr
+  int32_t *verdicts;  // the caller's nv_verdicts, or nullptr
   size_t ar = 0, nv = 0, nv0 = 0;
   uint32_t block = 0;
   void begin() { nv0 = nv; }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk) {
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk,
+            int32_t vd) {
+    if (verdicts) verdicts[nv] = vd;
     if (checks) {
       checks[2 * nv] = cn;
       checks[2 * nv + 1] = cv;
@@ -484,10 +530,41 @@ struct DirectSink {
   int32_t count() const { return (int32_t)(nv - nv0); }
 };
 
+// An _http call's view of one block: its mode, the stream's state (in: before
+// the block; out: after it) and the block's result.  After the first stream
+// error the reference stops calling nghttp2_http_on_header for the stream
+// (lib/nghttp2_session.c:3643-3664): the later fields are not examined and
+// the state stays.
+struct HttpRun {
+  uint32_t mode;
+  nghttp2_amd_hd_http_state st;
+  bool stopped = false;
+  int32_t result = 0;
+  int32_t step(const char *n, size_t nl, size_t vl, int8_t tk, uint8_t cn, uint8_t cv, uint32_t vf, int64_t vn) {
+    if (stopped) return NGHTTP2_AMD_HTTP_NOT_EXAMINED;
+    const int rv = hdhttp::on_header(&st, mode, hdhttp::Field{(const uint8_t *)n, nl, vl, tk, cn, cv, vf, vn});
+    if (rv == NGHTTP2_AMD_ERR_HTTP_HEADER) {
+      stopped = true;
+      result = rv;
+    }
+    return rv;
+  }
+  // the end of a block whose wire was sound: the block-end function of the mode
+  void end() {
+    if (stopped || (mode & NGHTTP2_AMD_HTTP_MODE_TRAILER)) return;
+    const int rv = (mode & NGHTTP2_AMD_HTTP_MODE_REQUEST) ? hdhttp::on_request_headers(&st, mode)
+                                                          : hdhttp::on_response_headers(&st);
+    if (rv) result = NGHTTP2_AMD_ERR_HTTP_MESSAGING;
+  }
+};
+
 // chk: a checked call -- every emitted name and value with its check mask.
 // tok: a tokened call -- every emitted field with its name's token.
+// http: an _http call (chk and tok are set) -- every emitted field with its
+// verdict, the block's state and result in *http.
 template <class Sink>
-void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, bool chk, bool tok, Sink &out) {
+void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, bool chk, bool tok, HttpRun *http,
+                  Sink &out) {
   out.begin();
   bool ok = !inf->bad;
   bool head = true;  // size updates only at the head of a block
@@ -513,6 +590,9 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     size_t nl, vl;
     uint8_t cn = kUnchecked, cv = kUnchecked;
     int8_t tk = kTokUnknown;
+    uint32_t vf = kFactUnknown;
+    int64_t vn = -1;
+    int32_t vd = 0;
     if (op.kind == Op::INDEXED) {  // hd_inflate_commit_indexed
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
@@ -521,7 +601,11 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       inf->entry(op.value - 1, &n, &nl, &v, &vl);
       if (chk) inf->entry_checks(op.value - 1, &cn, &cv);
       if (tok) tk = inf->entry_token(op.value - 1);
-      out.emit(n, nl, v, vl, 0, cn, cv, tk);
+      if (http) {
+        vf = inf->entry_facts(op.value - 1, &vn);
+        vd = http->step(n, nl, vl, tk, cn, cv, vf, vn);
+      }
+      out.emit(n, nl, v, vl, 0, cn, cv, tk, vd);
       continue;
     }
     if (op.new_name) {  // hd_inflate_commit_newname
@@ -549,9 +633,13 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     }
     if (chk) cv = ls.check(op.val);
     const uint8_t flags = op.no_index ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
-    out.emit(n, nl, v, vl, flags, cn, cv, tk);
+    if (http) {
+      vf = ls.facts(op.val, &vn);
+      vd = http->step(n, nl, vl, tk, cn, cv, vf, vn);
+    }
+    out.emit(n, nl, v, vl, flags, cn, cv, tk, vd);
     if (op.index_required)  // the table copies the field just emitted
-      inf->add(out.last_name(), nl, out.last_value(), vl, cn, cv, tk);
+      inf->add(out.last_name(), nl, out.last_value(), vl, cn, cv, tk, vf, vn);
   }
   // truncated or malformed wire after the parsed representations; and a
   // block that ends while a table size update is still expected
@@ -559,8 +647,10 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
   if (ok && (!b.parse_ok || inf->expect_size)) ok = false;
   if (!ok) {
     inf->bad = true;
+    if (http) http->result = NGHTTP2_AMD_ERR_HEADER_COMP;
     out.finish(NGHTTP2_AMD_ERR_HEADER_COMP);  // the fields before the error stay emitted
   } else {
+    if (http) http->end();
     out.finish(out.count());
   }
 }
@@ -578,6 +668,18 @@ struct Dest {
   int32_t *block_status;
   uint8_t *nv_checks;  // a checked call: two masks per field; else nullptr
   int32_t *nv_tokens;  // a tokened call: a token per field; else nullptr
+  // an _http call (block_modes given): a mode per block, the streams' states
+  // in and out, a verdict per field and a result per block (either may be
+  // nullptr); else all nullptr
+  const uint8_t *block_modes;
+  nghttp2_amd_hd_http_state *block_state;
+  int32_t *nv_verdicts, *block_http;
+  bool http() const { return block_modes != nullptr; }
+  HttpRun run(uint32_t i) const { return HttpRun{block_modes[i], block_state[i]}; }
+  void set_http(uint32_t i, const nghttp2_amd_hd_http_state &st, int32_t res) const {
+    block_state[i] = st;
+    if (block_http) block_http[i] = res;
+  }
 };
 
 // The parts of a parsed block's output bound: a field per representation,
@@ -702,7 +804,13 @@ int zc_mode() {
 // words and the masks and come back in that copy too.  Values get a token as
 // names do (pass 1 numbers the literals without telling them apart); the
 // replay reads the names' only.
-int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, void *stream, Phases &ph, LitSrc *ls) {
+// An _http call (checks and tokens are set) queues
+// nghttp2_amd_hd_http_facts_batch behind those two; the numbers, an int64 per
+// literal at the next 8-byte boundary behind the status words, and the facts,
+// a uint32 per literal behind them, come before the tokens and come back in
+// that copy as well.  Names get facts as values do; the replay reads the values' only.
+int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, bool http, void *stream, Phases &ph,
+                 LitSrc *ls) {
   for (uint32_t i = 0; i < nblocks; ++i) {
     E.nhuff[i + 1] += E.nhuff[i];
     E.hbytes[i + 1] += E.hbytes[i];
@@ -722,9 +830,14 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, void *st
   // at it when every literal is empty; the token lookup reads at most one
   // chunk past the chunk a literal ends in)
   const size_t out_alloc = out_bytes + (checks || tokens ? 16u : 0u);
-  // behind the status words: [tokens: nh int32] [checks: nh bytes]
+  // behind the status words: [pad to 8, numbers: nh int64, facts: nh uint32]
+  // [tokens: nh int32] [checks: nh bytes].  The status words end at byte
+  // 4 * (3 nh + 2) of the pool: a multiple of 8 when nh is even
   const size_t tok_bytes = tokens ? nh * sizeof(int32_t) : 0u, chk_bytes = checks ? nh : 0u;
-  const size_t slots = (size_t)nh + 1u, meta = 3u * slots * sizeof(uint32_t) + tok_bytes + chk_bytes;
+  const size_t http_pad = http && (nh & 1u) ? 4u : 0u;
+  const size_t http_bytes = http ? http_pad + nh * (sizeof(int64_t) + sizeof(uint32_t)) : 0u;
+  const size_t slots = (size_t)nh + 1u,
+               meta = 3u * slots * sizeof(uint32_t) + http_bytes + tok_bytes + chk_bytes;
   // (the output pool is a D2H copy target unless the kernel writes it
   // through the mapping, mode 1; the input pools are mapped unless mode 0;
   // mode 2 needs no device copy of the input)
@@ -736,7 +849,7 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, void *st
   ph.mark("pools");
   number_and_copy(E, nblocks);
   ph.mark("number+copy");
-  *ls = LitSrc{nullptr, nullptr, nullptr, nullptr, nullptr};
+  *ls = LitSrc{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (!nh) return 0;
   hipStream_t st = (hipStream_t)stream;
   uint32_t *const h_meta = E.h_meta.as<uint32_t>();
@@ -770,11 +883,17 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, void *st
   if (rv) return drain(rv);
   if (checks) {
     const int rc =
-        nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, (uint8_t *)(d_st + nh) + tok_bytes, stream);
+        nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, (uint8_t *)(d_st + nh) + http_bytes + tok_bytes, stream);
     if (rc) return drain(rc);
   }
   if (tokens) {
-    const int rc = nghttp2_amd_hd_name_tokens_len_batch(dst, d_slot, d_st, nh, d_st + nh, nullptr, stream);
+    const int rc = nghttp2_amd_hd_name_tokens_len_batch(dst, d_slot, d_st, nh,
+                                                        (int32_t *)((uint8_t *)(d_st + nh) + http_bytes), nullptr, stream);
+    if (rc) return drain(rc);
+  }
+  if (http) {
+    int64_t *d_num = (int64_t *)((uint8_t *)(d_st + nh) + http_pad);
+    const int rc = nghttp2_amd_hd_http_facts_batch(dst, d_slot, d_st, nh, (uint32_t *)(d_num + nh), d_num, stream);
     if (rc) return drain(rc);
   }
   uint32_t *h_slot = h_meta + slots;
@@ -782,11 +901,18 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, void *st
   if (!zero_copy &&
       (hipMemcpyAsync(E.h_out.p, dst, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
        hipMemcpyAsync(h_slot, d_slot, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t) + tok_bytes + chk_bytes, hipMemcpyDeviceToHost, st) !=
-           hipSuccess))
+       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t) + http_bytes + tok_bytes + chk_bytes, hipMemcpyDeviceToHost,
+                      st) != hipSuccess))
     return drain(NGHTTP2_AMD_ERR_FATAL);
-  *ls = LitSrc{E.h_out.as<uint8_t>(), h_slot, h_st, checks ? (const uint8_t *)(h_st + nh) + tok_bytes : nullptr,
-               tokens ? h_st + nh : nullptr};
+  const uint8_t *h_tail = (const uint8_t *)(h_st + nh);  // what follows the status words
+  const int64_t *h_num = (const int64_t *)(h_tail + http_pad);
+  *ls = LitSrc{E.h_out.as<uint8_t>(),
+               h_slot,
+               h_st,
+               checks ? h_tail + http_bytes + tok_bytes : nullptr,
+               tokens ? (const int32_t *)(h_tail + http_bytes) : nullptr,
+               http ? (const uint32_t *)(h_num + nh) : nullptr,
+               http ? h_num : nullptr};
   return 0;
 }
 
@@ -838,7 +964,7 @@ bool may_cut(const Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
 
 // One replayed block's fields into the caller's field array at nv_base and arena at ar_base.
 void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_base, nghttp2_amd_hd_nv *nva,
-                 uint8_t *arena, uint8_t *checks, int32_t *tokens) {
+                 uint8_t *arena, uint8_t *checks, int32_t *tokens, int32_t *verdicts) {
   const uint32_t ab = (uint32_t)ar_base;
   if (!o.bytes.empty()) memcpy(arena + ab, o.bytes.data(), o.bytes.size());
   nghttp2_amd_hd_nv *d = nva + nv_base;
@@ -852,6 +978,10 @@ void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_ba
     int32_t *t = tokens + nv_base;
     for (const Rec &r : o.recs) *t++ = r.tk;
   }
+  if (verdicts) {
+    int32_t *t = verdicts + nv_base;
+    for (const Rec &r : o.recs) *t++ = r.vd;
+  }
 }
 
 // "replay direct" -- pass 2 for a batch of one connection (a serial replay
@@ -864,8 +994,8 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
   if (ls.st && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
   ph.mark("gpu wait");
   nghttp2_amd_hd_inflater *c = E.conns[0];
-  DirectSink ds{d.arena, d.nva, d.block_status, d.nv_checks, d.nv_tokens};
-  const bool chk = d.nv_checks != nullptr, tok = d.nv_tokens != nullptr;
+  DirectSink ds{d.arena, d.nva, d.block_status, d.nv_checks, d.nv_tokens, d.nv_verdicts};
+  const bool htp = d.http(), chk = d.nv_checks != nullptr || htp, tok = d.nv_tokens != nullptr || htp;
   uint32_t cut = nblocks;
   for (uint32_t i = 0; i < nblocks; ++i) {
     const Block &b = E.bl[i];
@@ -873,25 +1003,31 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
     // in it, and in max_nl / max_vl)
     const uint64_t ar_b = block_ar_bound(b, dyn_ref_bound(c, b.lit_name, b.lit_val));
     ds.block = i;
+    HttpRun hr = htp ? d.run(i) : HttpRun{};
     if (ds.nv + b.nv <= d.nva_cap && ar_b <= d.arena_cap - ds.ar) {
-      replay_block(c, b, ls, chk, tok, ds);
+      replay_block(c, b, ls, chk, tok, htp ? &hr : nullptr, ds);
+      if (htp) d.set_http(i, hr.st, hr.result);
       continue;
     }
     nghttp2_amd_hd_inflater keep = *c;
     BlockOut scratch;
     BlockSink bs{scratch};
-    replay_block(c, b, ls, chk, tok, bs);
+    replay_block(c, b, ls, chk, tok, htp ? &hr : nullptr, bs);
     if (ds.nv + scratch.recs.size() > d.nva_cap || scratch.bytes.size() > d.arena_cap - ds.ar) {
       *c = std::move(keep);
       cut = i;
       break;
     }
-    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena, d.nv_checks, d.nv_tokens);
+    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena, d.nv_checks, d.nv_tokens, d.nv_verdicts);
+    if (htp) d.set_http(i, hr.st, hr.result);
     ds.nv += scratch.recs.size();
     ds.ar += scratch.bytes.size();
     d.block_status[i] = scratch.status;
   }
-  for (uint32_t j = cut; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+  for (uint32_t j = cut; j < nblocks; ++j) {
+    d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+    if (d.block_http) d.block_http[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;  // (its state stays as the caller put it)
+  }
   ph.mark("replay direct");
   *d.nva_used = ds.nv;
   *d.arena_used = ds.ar;
@@ -917,11 +1053,15 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
   // replay allocates only while they grow
   std::vector<BlockOut> &outs = E.outs;
   if (outs.size() < nblocks) outs.resize(nblocks);
-  const bool chk = d.nv_checks != nullptr, tok = d.nv_tokens != nullptr;
+  const bool htp = d.http(), chk = d.nv_checks != nullptr || htp, tok = d.nv_tokens != nullptr || htp;
   parallel_for(conns.size(), 1, [&](size_t c) {
     for (uint32_t j = E.cstart[c]; j < E.cstart[c + 1]; ++j) {
-      BlockSink bs{outs[E.corder[j]]};
-      replay_block(conns[c], E.bl[E.corder[j]], ls, chk, tok, bs);
+      const uint32_t i = E.corder[j];
+      BlockSink bs{outs[i]};
+      // (the caller's state is read here and written when the block is placed)
+      HttpRun hr = htp ? d.run(i) : HttpRun{};
+      replay_block(conns[c], E.bl[i], ls, chk, tok, htp ? &hr : nullptr, bs);
+      if (htp) outs[i].hst = hr.st, outs[i].hres = hr.result;
     }
   });
   ph.mark("replay");
@@ -949,12 +1089,23 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
     for (size_t c = 0; c < conns.size(); ++c) *conns[c] = std::move(snap[c]);
     BlockOut scratch;
     BlockSink ss{scratch};
-    for (uint32_t i = 0; i < cut; ++i) replay_block(inflaters[i], E.bl[i], ls, chk, tok, ss);
-    for (uint32_t j = cut; j < nblocks; ++j) d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+    // (the tables carry the values' facts as the first replay left them in
+    // the entries: the states are not written yet, so each block starts from
+    // the caller's again)
+    for (uint32_t i = 0; i < cut; ++i) {
+      HttpRun hr = htp ? d.run(i) : HttpRun{};
+      replay_block(inflaters[i], E.bl[i], ls, chk, tok, htp ? &hr : nullptr, ss);
+    }
+    for (uint32_t j = cut; j < nblocks; ++j) {
+      d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+      if (d.block_http) d.block_http[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+    }
   }
   parallel_for(cut, 256, [&](size_t i) {
-    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena, d.nv_checks, d.nv_tokens);
+    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena, d.nv_checks, d.nv_tokens,
+                d.nv_verdicts);
     d.block_status[i] = outs[i].status;
+    if (htp) d.set_http((uint32_t)i, outs[i].hst, outs[i].hres);
   });
   ph.mark("place");
   *d.nva_used = nv_base[cut];
@@ -1081,6 +1232,18 @@ int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_inflater *const *inflate
                                          uint8_t *arena, size_t arena_cap, size_t *arena_used,
                                          int32_t *block_status, uint8_t *nv_checks, int32_t *nv_tokens,
                                          void *stream) {
+  return nghttp2_amd_hd_inflate_blocks_http(inflaters, nblocks, blocks, block_lens, nva, nva_cap, nva_used, arena,
+                                            arena_cap, arena_used, block_status, nv_checks, nv_tokens, nullptr,
+                                            nullptr, nullptr, nullptr, stream);
+}
+
+int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks,
+                                       const uint8_t *const *blocks, const size_t *block_lens,
+                                       nghttp2_amd_hd_nv *nva, size_t nva_cap, size_t *nva_used, uint8_t *arena,
+                                       size_t arena_cap, size_t *arena_used, int32_t *block_status,
+                                       uint8_t *nv_checks, int32_t *nv_tokens, const uint8_t *block_modes,
+                                       nghttp2_amd_hd_http_state *block_state, int32_t *nv_verdicts,
+                                       int32_t *block_http, void *stream) {
   if (nva_used) *nva_used = 0;
   if (arena_used) *arena_used = 0;
   if (nblocks == 0) return 0;
@@ -1088,16 +1251,22 @@ int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_inflater *const *inflate
     return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < nblocks; ++i)
     if (!inflaters[i] || (!blocks[i] && block_lens[i])) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  // an _http call: the modes and the states are its input, so both are needed
+  const bool http = block_modes || block_state || nv_verdicts || block_http;
+  if (http && (!block_modes || !block_state)) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
 
   nghttp2_amd_host::Pool::CallScope scope;  // workers spin between this call's phases only
   Phases ph("inflate");
   std::lock_guard<std::mutex> guard(engine().mu);
   Engine &E = engine();
-  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status, nv_checks, nv_tokens};
+  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status, nv_checks, nv_tokens,
+                  block_modes, block_state, nv_verdicts, block_http};
   parse_blocks(E, nblocks, blocks, block_lens);
   ph.mark("parse blocks");
   LitSrc ls;
-  if (const int rv = stage_decode(E, nblocks, nv_checks != nullptr, nv_tokens != nullptr, stream, ph, &ls)) return rv;
+  if (const int rv = stage_decode(E, nblocks, nv_checks != nullptr || http, nv_tokens != nullptr || http, http, stream,
+                                   ph, &ls))
+    return rv;
   ph.mark("gpu issued");
   // (the decode runs while the host groups the blocks by connection and
   // bounds the output; replay waits for it)

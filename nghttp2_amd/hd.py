@@ -48,6 +48,46 @@ CHECK_INVALID = 0x80          # the string was not examined
 TOKEN_NONE = -1               # examined, not a token name (lookup_token's -1)
 TOKEN_INVALID = -2            # the string was not examined
 
+# http_facts / http_facts_batch / inflate_blocks(http=...): the value facts of
+# nghttp2_http_on_header (lib/nghttp2_http.c), a bit set exactly when the
+# reference's test passes
+HTTP_FACT_AUTHORITY = 0x001      # check_authority (no '@')
+HTTP_FACT_SCHEME = 0x002         # check_scheme
+HTTP_FACT_SCHEME_HTTP = 0x004    # "http" / "https", any case
+HTTP_FACT_METH_HEAD = 0x008
+HTTP_FACT_METH_CONNECT = 0x010
+HTTP_FACT_METH_OPTIONS = 0x020
+HTTP_FACT_PATH_SLASH = 0x040     # first byte '/'
+HTTP_FACT_PATH_ASTERISK = 0x080  # "*"
+HTTP_FACT_TE_TRAILERS = 0x100    # "trailers", any case
+HTTP_FACT_LWS = 0x200            # SP / HT only
+HTTP_FACT_UINT = 0x400           # parse_uint succeeds
+HTTP_FACT_INVALID = 0x80000000   # the string was not examined
+
+HTTP_MODE_REQUEST = 0x01           # session->server or a PUSH_PROMISE; clear: a response
+HTTP_MODE_PUSH = 0x02              # even stream id
+HTTP_MODE_TRAILER = 0x04
+HTTP_MODE_CONNECT_PROTOCOL = 0x08  # the extended CONNECT setting is enabled
+HTTP_MODE_NO_RFC9113_WS = 0x10
+
+NGHTTP2_ERR_IGN_HTTP_HEADER = -105
+NGHTTP2_ERR_REMOVE_HTTP_HEADER = -106
+NGHTTP2_ERR_HTTP_HEADER = -531
+NGHTTP2_ERR_HTTP_MESSAGING = -532
+HTTP_NOT_EXAMINED = 1            # a field after the block's first NGHTTP2_ERR_HTTP_HEADER
+
+
+class HttpState(ctypes.Structure):
+    """nghttp2_amd_hd_http_state: the stream's http_flags, status_code and
+    content_length; a fresh stream is HttpState(0, -1, -1)."""
+    _fields_ = [("http_flags", ctypes.c_uint32), ("status_code", ctypes.c_int32),
+                ("content_length", ctypes.c_int64)]
+
+
+_HTTP_STATE_DTYPE = np.dtype([("http_flags", "<u4"), ("status_code", "<i4"),
+                              ("content_length", "<i8")])
+assert _HTTP_STATE_DTYPE.itemsize == ctypes.sizeof(HttpState)
+
 _lib = None
 
 
@@ -105,6 +145,14 @@ def lib():
         L.nghttp2_amd_hd_check_field.argtypes = [ctypes.c_char_p, sz]
         L.nghttp2_amd_hd_check_field.restype = ctypes.c_uint8
         L.nghttp2_amd_hd_check_fields_batch.argtypes = [vp, vp, vp, u32, vp, vp]
+        L.nghttp2_amd_hd_http_facts.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int64)]
+        L.nghttp2_amd_hd_http_facts.restype = ctypes.c_uint32
+        L.nghttp2_amd_hd_http_facts_batch.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+        L.nghttp2_amd_hd_http_on_header.argtypes = [
+            ctypes.POINTER(HttpState), u32, ctypes.c_char_p, sz, sz, ctypes.c_int32, ctypes.c_uint8,
+            ctypes.c_uint8, u32, ctypes.c_int64]
+        L.nghttp2_amd_hd_http_on_request_headers.argtypes = [ctypes.POINTER(HttpState), u32]
+        L.nghttp2_amd_hd_http_on_response_headers.argtypes = [ctypes.POINTER(HttpState)]
         _lib = L
     return _lib
 
@@ -126,6 +174,34 @@ def check_field(s):
     CHECK_* mask."""
     s = bytes(s)
     return lib().nghttp2_amd_hd_check_field(s, len(s))
+
+
+def http_facts(s):
+    """Host value facts of one string (lib/nghttp2_http.c's check_authority,
+    check_scheme, lws, parse_uint and literal comparisons): (HTTP_FACT_* bits,
+    parse_uint's value or -1)."""
+    s = bytes(s)
+    num = ctypes.c_int64()
+    f = lib().nghttp2_amd_hd_http_facts(s, len(s), ctypes.byref(num))
+    return f, num.value
+
+
+def http_on_header(state, mode, name, value_len, token, name_mask, value_mask, value_facts,
+                   value_number):
+    """nghttp2_http_on_header for one field from its token, masks and facts;
+    updates state (an HttpState) and returns the verdict."""
+    name = bytes(name)
+    return lib().nghttp2_amd_hd_http_on_header(ctypes.byref(state), mode, name, len(name), value_len,
+                                               token, name_mask, value_mask, value_facts,
+                                               value_number)
+
+
+def http_on_request_headers(state, mode):
+    return lib().nghttp2_amd_hd_http_on_request_headers(ctypes.byref(state), mode)
+
+
+def http_on_response_headers(state):
+    return lib().nghttp2_amd_hd_http_on_response_headers(ctypes.byref(state))
 
 
 def tables_ref_layout():
@@ -279,6 +355,21 @@ class HuffmanBatchCodec:
         _check(rv, "check_fields_batch")
         return mask[:n]
 
+    def http_facts_batch(self, pool, off, len=None, facts=None, number=None, stream=None):
+        """The value facts of nghttp2_http_on_header for every string of the
+        batch, in check_fields' layouts: returns (facts int32[n] holding the
+        uint32 HTTP_FACT_* bits, number int64[n] = parse_uint's value or -1).
+        A string with a negative or overrunning len gets HTTP_FACT_INVALID."""
+        n = off.numel() - 1
+        if facts is None:
+            facts = self._empty(max(1, n), self.torch.int32, stream)
+        if number is None:
+            number = self._empty(max(1, n), self.torch.int64, stream)
+        rv = self.L.nghttp2_amd_hd_http_facts_batch(
+            _p(pool), _p(off), _p(len), n, _p(facts), _p(number), _stream(stream))
+        _check(rv, "http_facts_batch")
+        return facts[:n], number[:n]
+
     def emit_strings(self, src, src_off, raw_bytes=None, dst=None, dst_off=None, stream=None):
         """HPACK string literals (emit_string, lib/nghttp2_hd.c:1001-1044) for
         every string: returns (dst pool, dst_off int32[n+1]); literal i is
@@ -431,6 +522,10 @@ def _inflate_lib():
         L.nghttp2_amd_hd_inflate_blocks_fields.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, sz,
                                                            ctypes.POINTER(sz), vp, sz,
                                                            ctypes.POINTER(sz), vp, vp, vp, vp]
+        L.nghttp2_amd_hd_inflate_blocks_http.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, sz,
+                                                         ctypes.POINTER(sz), vp, sz,
+                                                         ctypes.POINTER(sz), vp, vp, vp, vp, vp, vp,
+                                                         vp, vp]
         L._inflate_bound = True
     return L
 
@@ -486,7 +581,7 @@ assert _NV_DTYPE.itemsize == ctypes.sizeof(_Nv)
 
 
 def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None, retry=True,
-                   checks=False, tokens=False):
+                   checks=False, tokens=False, http=None, http_state=None):
     """Inflate complete header blocks, block i against inflaters[i], with
     every Huffman literal decoded in one GPU batch.  Returns
     (status[i], fields[i] = [(name, value, flags)]).  A batch that outgrows
@@ -500,10 +595,29 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
     result follows (after the masks when both are asked for): an int32 array
     (nfields,) of lookup_token of every emitted field's name, as
     nghttp2_hd_inflate_hd_nv sets nv.token.
+    With http (one HTTP_MODE_* value per block) the call is
+    nghttp2_amd_hd_inflate_blocks_http and three more results follow: an int32
+    array (nfields,) of nghttp2_http_on_header's verdict for every emitted
+    field (HTTP_NOT_EXAMINED after a block's first stream error), a structured
+    array (nblocks,) of the streams' states after their blocks (http_flags,
+    status_code, content_length), and a list of the blocks' results (0,
+    NGHTTP2_ERR_HTTP_HEADER, NGHTTP2_ERR_HTTP_MESSAGING or
+    NGHTTP2_ERR_HEADER_COMP).  http_state gives the states before the blocks,
+    one (http_flags, status_code, content_length) per block; None is a fresh
+    stream, (0, -1, -1), for every block.
     The blocks go in as one joined buffer and the fields come out of
     uninitialised numpy buffers (no per-block ctypes objects, no zero fill)."""
     L = _inflate_lib()
     nb = len(blocks)
+    if http is not None:
+        modes_all = np.fromiter((int(m) for m in http), dtype=np.uint8, count=nb)
+        states_all = np.empty(nb, dtype=_HTTP_STATE_DTYPE)
+        if http_state is None:
+            states_all[:] = (0, -1, -1)
+        else:
+            for i, t in enumerate(http_state):
+                states_all[i] = tuple(t)
+        bhttp_all = np.full(nb, NGHTTP2_ERR_BUFFER_ERROR, dtype=np.int32)
     joined = b"".join(bytes(b) for b in blocks)
     total = len(joined)
     lens_all = np.fromiter((len(b) for b in blocks), dtype=np.uint64, count=nb)
@@ -527,7 +641,7 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
             s = None
     status = [NGHTTP2_ERR_BUFFER_ERROR] * nb
     fields = [[] for _ in range(nb)]
-    masks, toks = [], []
+    masks, toks, verds = [], [], []
     first = 0
     vp = ctypes.c_void_p
     while first < nb:
@@ -539,7 +653,19 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
         arena = np.empty(max(1, arena_cap), dtype=np.uint8)
         st = np.empty(m, dtype=np.int32)
         nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
-        if tokens:
+        if http is not None:
+            chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8) if checks else None
+            tk = np.empty(max(1, nva_cap), dtype=np.int32) if tokens else None
+            vd = np.empty(max(1, nva_cap), dtype=np.int32)
+            # (views of the callers' slices: the states are updated in place)
+            rv = L.nghttp2_amd_hd_inflate_blocks_http(
+                vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
+                vp(nva.ctypes.data), nva_cap, ctypes.byref(nv_used), vp(arena.ctypes.data),
+                arena_cap, ctypes.byref(ar_used), vp(st.ctypes.data),
+                vp(chk.ctypes.data) if checks else None, vp(tk.ctypes.data) if tokens else None,
+                vp(modes_all[first:].ctypes.data), vp(states_all[first:].ctypes.data),
+                vp(vd.ctypes.data), vp(bhttp_all[first:].ctypes.data), s)
+        elif tokens:
             chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8) if checks else None
             tk = np.empty(max(1, nva_cap), dtype=np.int32)
             rv = L.nghttp2_amd_hd_inflate_blocks_fields(
@@ -566,6 +692,8 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
             masks.append(chk[:nv_used.value].copy())
         if tokens:
             toks.append(tk[:nv_used.value].copy())
+        if http is not None:
+            verds.append(vd[:nv_used.value].copy())
         for b, no, nl, vo, vl, fl in zip((nv["block"] + first).tolist(), nv["name_off"].tolist(),
                                          nv["name_len"].tolist(), nv["value_off"].tolist(),
                                          nv["value_len"].tolist(), nv["flags"].tolist()):
@@ -586,6 +714,9 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
         res += (np.concatenate(masks) if masks else np.zeros((0, 2), np.uint8),)
     if tokens:
         res += (np.concatenate(toks) if toks else np.zeros(0, np.int32),)
+    if http is not None:
+        res += (np.concatenate(verds) if verds else np.zeros(0, np.int32), states_all,
+                bhttp_all.tolist())
     return res
 
 

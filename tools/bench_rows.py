@@ -31,6 +31,14 @@
            build of the library (the parent commit's), its _checked against
            this build's in the same process: the existing call must not have
            become slower.
+  http_facts  nghttp2_amd_hd_http_facts_batch against
+           nghttp2_amd_hd_check_fields_batch on the check row's two pools,
+           alternated call by call: the same walk, loads and ballots, plus
+           the string lane's own reads; and on 4,096 numbers of 16 KiB of zeros.
+  inflate_http  nghttp2_amd_hd_inflate_blocks_http against
+           nghttp2_amd_hd_inflate_blocks_fields with both arrays on the
+           2,048-block batch, alternated; with NGHTTP2_AMD_OTHER_LIB, that
+           build's _fields against this build's in the same process.
 
 Prints one JSON object.  Not the bench.py contract (that is the hot path
 itself); the numbers go to DESIGN.md."""
@@ -332,6 +340,166 @@ def bench_inflate_fields(nconn=256, per_conn=8, fields=16, alternations=15):
     return out
 
 
+def bench_http_facts(steps=30):
+    """http_facts_batch against check_fields, alternated call by call on the
+    check row's two device-resident pools in one process; each call between
+    two HIP events, the best of the steps of each.  The yardstick is the
+    same walk with the same loads."""
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import workloads as W
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from tests import http_fields_ref as R
+    dev = torch.device("cuda:0")
+    codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    n = 1 << 20
+    out = {}
+    # a pool a peer could send: 4,096 numbers of 16 KiB, all '0' but a last digit
+    nz, lz = 4096, 16384
+    zeros = np.full(nz * lz + 32, ord("0"), dtype=np.uint8)
+    zeros[lz - 1:nz * lz:lz] = ord("7")
+    zoff = (np.arange(nz + 1, dtype=np.uint64) * lz).astype(np.uint32)
+    for label, (pool, off) in (("mixed_1M", W.gen_mixed_range(W.mixed_lengths(n), 0, n, threads=8)),
+                               ("pseudo_1M", W.gen_pseudo_headers(n)),
+                               ("zeros_16K_x4096", (zeros, zoff))):
+        n = len(off) - 1
+        raw = int(off[-1])
+        src = torch.from_numpy(pool).to(dev)
+        so = torch.from_numpy(off.view(np.int32)).to(dev)
+        mask = codec.check_fields(src, so)
+        facts, number = codec.http_facts_batch(src, so)
+        torch.cuda.synchronize()
+        k = min(n, 5000) if label != "zeros_16K_x4096" else 64  # parity on a sample
+        gf, gn = facts[:k].cpu().numpy().view(np.uint32), number[:k].cpu().numpy()
+        assert all((int(gf[i]), int(gn[i])) == R.facts(pool[off[i]:off[i + 1]].tobytes()) for i in range(k))
+        s = torch.cuda.current_stream()
+        for _ in range(5):
+            codec.http_facts_batch(src, so, facts=facts, number=number)
+            codec.check_fields(src, so, mask=mask)
+        ev = []
+        for _ in range(steps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record(s)
+            codec.http_facts_batch(src, so, facts=facts, number=number)
+            e[1].record(s)
+            e[2].record(s)
+            codec.check_fields(src, so, mask=mask)
+            e[3].record(s)
+            ev.append(e)
+        torch.cuda.synchronize()
+        th = min(e[0].elapsed_time(e[1]) for e in ev) * 1e-3
+        tc = min(e[2].elapsed_time(e[3]) for e in ev) * 1e-3
+        out[label] = {"strings": n, "raw_bytes": raw, "http_facts_us": round(th * 1e6, 2),
+                      "check_us": round(tc * 1e6, 2), "http_facts_over_check": round(th / tc, 3),
+                      "http_facts_GBps_R_plus_16N": round((raw + 16 * n) / th / 1e9, 1),
+                      "check_GBps_R_plus_5N": round((raw + 5 * n) / tc / 1e9, 1),
+                      "http_facts_us_median": round(float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e3, 2),
+                      "check_us_median": round(float(np.median([e[2].elapsed_time(e[3]) for e in ev])) * 1e3, 2)}
+    return out
+
+
+def bench_inflate_http(nconn=256, per_conn=8, fields=16, alternations=15):
+    """The C call of the 2,048-block inflate row, alternated call by call (no
+    indexing: every call sees the same tables): _fields with both arrays and
+    _http with all its arrays; with NGHTTP2_AMD_OTHER_LIB, that build's
+    _fields too.  Every block is run as a request on a fresh state, so every
+    one of its fields is stepped (asserted: no field is left unexamined) and
+    the request's block end runs."""
+    import ctypes
+    import statistics
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    blocks, conns = make_blocks(nconn, per_conn, fields)
+    wire = sum(len(b) for b in blocks)
+    L = hd._inflate_lib()
+    m = len(blocks)
+    keep = [ctypes.create_string_buffer(b, len(b)) for b in blocks]
+    ptrs = (ctypes.c_void_p * m)(*[ctypes.cast(k, ctypes.c_void_p) for k in keep])
+    lens = (ctypes.c_size_t * m)(*[len(b) for b in blocks])
+    nva_cap, arena_cap = wire + 16, 8 * wire + 4096
+    nva = (hd._Nv * nva_cap)()
+    arena = (ctypes.c_uint8 * arena_cap)()
+    chk = (ctypes.c_uint8 * (2 * nva_cap))()
+    tk = (ctypes.c_int32 * nva_cap)()
+    vd = (ctypes.c_int32 * nva_cap)()
+    stc = (ctypes.c_int32 * m)()
+    bh = (ctypes.c_int32 * m)()
+    modes = (ctypes.c_uint8 * m)()
+    states = (hd.HttpState * m)()
+    for i in range(m):
+        modes[i] = hd.HTTP_MODE_REQUEST
+    nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
+    import torch
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+    ip = (ctypes.c_void_p * m)(*[infs[c].p.value for c in conns])
+
+    def timed(f):
+        def g():
+            t0 = time.perf_counter()
+            rv = f()
+            dt = time.perf_counter() - t0
+            assert rv == 0
+            return dt
+        return g
+
+    def http_call():
+        for i in range(m):
+            states[i].http_flags, states[i].status_code, states[i].content_length = 0, -1, -1
+        return timed(lambda: L.nghttp2_amd_hd_inflate_blocks_http(
+            ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
+            chk, tk, modes, states, vd, bh, s))()
+    calls = {"fields": timed(lambda: L.nghttp2_amd_hd_inflate_blocks_fields(
+        ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
+        chk, tk, s)), "http": http_call}
+    other = os.environ.get("NGHTTP2_AMD_OTHER_LIB")
+    if other:
+        P = ctypes.CDLL(other)
+        vp = ctypes.c_void_p
+        P.nghttp2_amd_hd_inflate_new.argtypes = [ctypes.POINTER(vp)]
+        P.nghttp2_amd_hd_inflate_blocks_fields.argtypes = L.nghttp2_amd_hd_inflate_blocks_fields.argtypes
+        pin = []
+        for _ in range(nconn):
+            q = vp()
+            assert P.nghttp2_amd_hd_inflate_new(ctypes.byref(q)) == 0
+            pin.append(q.value)
+        pip = (ctypes.c_void_p * m)(*[pin[c] for c in conns])
+        calls["other_fields"] = timed(lambda: P.nghttp2_amd_hd_inflate_blocks_fields(
+            pip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
+            chk, tk, s))
+    for _ in range(3):
+        for c in calls.values():
+            c()
+    ts = {k: [] for k in calls}
+    for _ in range(alternations):
+        for k, c in calls.items():
+            ts[k].append(c())
+    # what the last _http call left: every field stepped, every block ended
+    http_call()
+    verdicts = np.frombuffer(vd, dtype=np.int32)[:nv_used.value]
+    results = np.frombuffer(bh, dtype=np.int32)[:m]
+    assert not np.any(verdicts == hd.HTTP_NOT_EXAMINED) and not np.any(verdicts == hd.NGHTTP2_ERR_HTTP_HEADER)
+    assert not np.any(results == hd.NGHTTP2_ERR_HTTP_HEADER)
+    out = {"blocks": m, "connections": nconn, "fields": nv_used.value, "wire_bytes": wire,
+           "alternations": alternations, "mode": "request",
+           "fields_stepped": int(verdicts.size), "verdicts_ok": int(np.sum(verdicts == 0)),
+           "verdicts_ignored": int(np.sum(verdicts == hd.NGHTTP2_ERR_IGN_HTTP_HEADER)),
+           "blocks_ok": int(np.sum(results == 0)),
+           "blocks_messaging_error": int(np.sum(results == hd.NGHTTP2_ERR_HTTP_MESSAGING))}
+    for k, v in ts.items():
+        out[k + "_s_best"] = round(min(v), 6)
+        out[k + "_s_median"] = round(statistics.median(v), 6)
+        out[k + "_s_worst"] = round(max(v), 6)
+    out["http_minus_fields_us_median"] = round((out["http_s_median"] - out["fields_s_median"]) * 1e6, 1)
+    out["http_minus_fields_us_best"] = round((out["http_s_best"] - out["fields_s_best"]) * 1e6, 1)
+    if other:
+        out["fields_minus_other_fields_us_median"] = round(
+            (out["fields_s_median"] - out["other_fields_s_median"]) * 1e6, 1)
+        out["fields_minus_other_fields_us_best"] = round(
+            (out["fields_s_best"] - out["other_fields_s_best"]) * 1e6, 1)
+    return out
+
+
 def bench_inflate_checked(nconn=256, per_conn=8, fields=16, alternations=15):
     """The C call of the 2,048-block inflate row with and without nv_checks,
     alternated call by call (no indexing: every call sees the same tables);
@@ -558,5 +726,7 @@ if __name__ == "__main__":
            "inflate_checked": bench_inflate_checked,
            "names_len": bench_names_len,
            "inflate_fields": bench_inflate_fields,
+           "http_facts": bench_http_facts,
+           "inflate_http": bench_inflate_http,
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
