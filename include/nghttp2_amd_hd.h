@@ -47,6 +47,7 @@ extern "C" {
 /* nghttp2_error values used on this path (lib/includes/nghttp2/nghttp2.h) */
 #define NGHTTP2_AMD_ERR_INVALID_ARGUMENT (-501) /* nghttp2.h:278 */
 #define NGHTTP2_AMD_ERR_BUFFER_ERROR (-502)     /* nghttp2.h:282 */
+#define NGHTTP2_AMD_ERR_INVALID_STATE (-519)    /* nghttp2.h:366 */
 #define NGHTTP2_AMD_ERR_HEADER_COMP (-523)      /* nghttp2.h:378 */
 #define NGHTTP2_AMD_ERR_INSUFF_BUFSIZE (-525)   /* nghttp2.h:386 */
 #define NGHTTP2_AMD_ERR_FATAL (-900)            /* nghttp2.h:451 (HIP error) */
@@ -533,7 +534,10 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_new(nghttp2_amd_hd_inflater **infl
 NGHTTP2_AMD_EXTERN void nghttp2_amd_hd_inflate_del(nghttp2_amd_hd_inflater *inflater);
 /* nghttp2_hd_inflate_change_table_size (nghttp2.h:6331): a smaller value
  * than the current maximum requires a size update at the head of the next
- * block. */
+ * block.  After a block that failed in the middle of a representation (any
+ * NGHTTP2_AMD_ERR_HEADER_COMP but that of a missing expected size update) it
+ * returns NGHTTP2_AMD_ERR_INVALID_STATE and changes nothing, as the
+ * reference's does for an inflater left where its block failed. */
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_change_table_size(nghttp2_amd_hd_inflater *inflater,
                                              size_t settings_max_dynamic_table_size);
 /* nghttp2_hd_inflate_get_num_table_entries / get_table_entry /

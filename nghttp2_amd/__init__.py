@@ -21,6 +21,7 @@ from .hd import (  # noqa: F401
     HuffmanBatchCodec,
     NGHTTP2_ERR_BUFFER_ERROR,
     NGHTTP2_ERR_HEADER_COMP,
+    NGHTTP2_ERR_INVALID_STATE,
     NGHTTP2_ERR_INSUFF_BUFSIZE,
     NGHTTP2_ERR_INVALID_ARGUMENT,
     TOKEN_INVALID,

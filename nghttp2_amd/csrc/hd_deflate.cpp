@@ -415,8 +415,10 @@ void for_each_run(const Batch &B, size_t i, const Framed &fr, F &&f) {
 
 // "wire" -- pass 2: each block's wire size, placement in block order, then
 // the bytes.  Returns 0, or BUFFER_ERROR when a block did not fit.
+// *stop_piece (a single-block call's, or null): the piece of a block that did
+// not fit at which the room ran out.
 int place_wire(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks, const Batch &B, const Framed &fr,
-               uint8_t *out, size_t out_cap, uint32_t *out_off, int32_t *block_status) {
+               uint8_t *out, size_t out_cap, uint32_t *out_off, int32_t *block_status, uint32_t *stop_piece) {
   std::vector<size_t> need(nblocks, 0);
   parallel_for(nblocks, 256, [&](size_t i) {
     size_t n = 0;
@@ -436,6 +438,21 @@ int place_wire(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks, cons
       block_status[i] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
       deflaters[i]->bad = true;
       ret = NGHTTP2_AMD_ERR_BUFFER_ERROR;
+      if (stop_piece) {
+        size_t n = o;
+        uint32_t k = 0;
+        for (const Piece &pc : B.pieces[i]) {
+          n += pc.bytes.size();
+          for (int j = 0; j < 2; ++j)
+            if (pc.lit[j] >= 0) {
+              const uint32_t g = B.litbase[i] + (uint32_t)pc.lit[j];
+              n += fr.off[g + 1] - fr.off[g];
+            }
+          if (n > out_cap) break;
+          ++k;
+        }
+        *stop_piece = k;
+      }
     } else if (block_status[i] == 0) {
       block_status[i] = (int32_t)need[i];
       o += need[i];
@@ -534,10 +551,12 @@ size_t nghttp2_amd_hd_deflate_bound(nghttp2_amd_hd_deflater *d, const nghttp2_am
   return n;
 }
 
-int nghttp2_amd_hd_deflate_blocks(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks,
-                                  const nghttp2_amd_nv *nva, const uint32_t *block_nv_off,
-                                  uint8_t *out, size_t out_cap, uint32_t *out_off,
-                                  int32_t *block_status, void *stream) {
+}  // extern "C"
+
+namespace {
+int deflate_blocks_impl(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks, const nghttp2_amd_nv *nva,
+                        const uint32_t *block_nv_off, uint8_t *out, size_t out_cap, uint32_t *out_off,
+                        int32_t *block_status, void *stream, uint32_t *stop_piece) {
   if (nblocks == 0) {
     if (out_off) out_off[0] = 0;
     return 0;
@@ -577,9 +596,20 @@ int nghttp2_amd_hd_deflate_blocks(nghttp2_amd_hd_deflater *const *deflaters, uin
   Framed fr;
   if (const int rv = frame_literals(engine(), nblocks, B, stream, &fr)) return fail_batch(rv);
   ph.mark("gpu");
-  const int ret = place_wire(deflaters, nblocks, B, fr, out, out_cap, out_off, block_status);
+  const int ret = place_wire(deflaters, nblocks, B, fr, out, out_cap, out_off, block_status, stop_piece);
   ph.mark("wire");
   return ret;
+}
+}  // namespace
+
+extern "C" {
+
+int nghttp2_amd_hd_deflate_blocks(nghttp2_amd_hd_deflater *const *deflaters, uint32_t nblocks,
+                                  const nghttp2_amd_nv *nva, const uint32_t *block_nv_off,
+                                  uint8_t *out, size_t out_cap, uint32_t *out_off,
+                                  int32_t *block_status, void *stream) {
+  return deflate_blocks_impl(deflaters, nblocks, nva, block_nv_off, out, out_cap, out_off, block_status, stream,
+                             nullptr);
 }
 
 ptrdiff_t nghttp2_amd_hd_deflate_hd2(nghttp2_amd_hd_deflater *deflater, uint8_t *buf, size_t buflen,
@@ -590,9 +620,28 @@ ptrdiff_t nghttp2_amd_hd_deflate_hd2(nghttp2_amd_hd_deflater *deflater, uint8_t 
   uint32_t out_off[2] = {0, 0};
   int32_t st = 0;
   uint8_t none = 0;
-  const int rv = nghttp2_amd_hd_deflate_blocks(&deflater, 1, nva, nv_off, buf ? buf : &none, buflen,
-                                               out_off, &st, stream);
-  if (st == NGHTTP2_AMD_ERR_BUFFER_ERROR) return NGHTTP2_AMD_ERR_INSUFF_BUFSIZE;  // :1546-1547
+  // (the table before the block: see below)
+  std::unique_ptr<nghttp2_amd_hd_deflater> before(deflater->bad ? nullptr : new nghttp2_amd_hd_deflater(*deflater));
+  uint32_t stop = 0;
+  const int rv = deflate_blocks_impl(&deflater, 1, nva, nv_off, buf ? buf : &none, buflen, out_off, &st, stream,
+                                     &stop);
+  if (st == NGHTTP2_AMD_ERR_BUFFER_ERROR) {  // :1546-1547
+    // The reference deflates field by field and stops at the representation
+    // that does not fit, after that field's table insertion (deflate_nv
+    // inserts, then emits); the passes above have inserted every field of the
+    // list.  So the table is put back and the fields up to that one are
+    // deflated again (stop counts the pending size updates' piece).
+    if (before) {
+      const uint32_t lead = before->notify ? 1u : 0u;
+      const uint32_t nfields = stop < lead ? 0u : std::min<uint32_t>(stop - lead + 1u, (uint32_t)nvlen);
+      *deflater = std::move(*before);
+      std::vector<Piece> P;
+      Lits L;
+      deflate_block(deflater, nva, nfields, nullptr, 0, P, L);
+      deflater->bad = true;
+    }
+    return NGHTTP2_AMD_ERR_INSUFF_BUFSIZE;
+  }
   if (st < 0) return st;
   if (rv < 0) return rv;
   return (ptrdiff_t)st;

@@ -142,6 +142,11 @@ struct nghttp2_amd_hd_inflater {
   size_t max_nl = 0, max_vl = 0;                // longest name / value ever inserted (bounds)
   bool expect_size = false;                     // NGHTTP2_HD_STATE_EXPECT_TABLE_SIZE
   bool bad = false;                             // ctx.bad
+  // a block failed outside NGHTTP2_HD_STATE_EXPECT_TABLE_SIZE: fail: (:2283-2287)
+  // leaves the state where it was and the caller of a failed block does not
+  // call end_headers (lib/nghttp2_session.c:3556-3690), so
+  // nghttp2_hd_inflate_change_table_size answers INVALID_STATE from then on
+  bool mid_block = false;
   uint64_t batch_gen = 0;                       // the inflate_blocks call that last grouped it
   uint32_t batch_conn = 0;                      // its connection number in that call
 
@@ -279,6 +284,7 @@ struct Op {
 struct alignas(128) Block {  // (aligned as BlockOut)
   std::vector<Op> ops;
   bool parse_ok = true;
+  bool first_is_size = false;  // the block's first byte opens a table size update
   // the output bound's parts (pass 1): fields, bytes other than dynamic-table
   // references, and the number of those references
   uint64_t nv = 0, ar = 0, ndyn = 0;
@@ -367,6 +373,7 @@ bool parse_block(const uint8_t *in, size_t len, Block &b) {
     return true;
   };
   b.ops.clear();  // (kept across calls: no allocation once grown)
+  b.first_is_size = len > 0 && (in[0] & 0xE0u) == 0x20u;
   b.ops.reserve(len / 4 + 1);
   while (pos < len) {
     Op op;
@@ -646,6 +653,11 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
   // (lib/nghttp2_hd.c:2259-2266)
   if (ok && (!b.parse_ok || inf->expect_size)) ok = false;
   if (!ok) {
+    // Where the reference's state stays: a block that starts while an update
+    // is expected and does not open with one fails on its first byte (or at
+    // its end, being empty) still in EXPECT_TABLE_SIZE (:1942-1949,
+    // :2259-2266); every other failure is in the middle of a representation.
+    if (!inf->bad) inf->mid_block = !(inf->expect_size && !b.first_is_size);
     inf->bad = true;
     if (http) http->result = NGHTTP2_AMD_ERR_HEADER_COMP;
     out.finish(NGHTTP2_AMD_ERR_HEADER_COMP);  // the fields before the error stay emitted
@@ -1175,6 +1187,7 @@ void nghttp2_amd_hd_inflate_del(nghttp2_amd_hd_inflater *inflater) { delete infl
 int nghttp2_amd_hd_inflate_change_table_size(nghttp2_amd_hd_inflater *inf,
                                              size_t settings_max_dynamic_table_size) {
   if (!inf) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  if (inf->mid_block) return NGHTTP2_AMD_ERR_INVALID_STATE;  // :1292-1298
   inf->settings_max = settings_max_dynamic_table_size;
   if (inf->bufsize_max > settings_max_dynamic_table_size) {
     inf->expect_size = true;

@@ -29,6 +29,7 @@ LIB_NAME = "libnghttp2_amd_hd.so"
 
 NGHTTP2_ERR_INVALID_ARGUMENT = -501
 NGHTTP2_ERR_BUFFER_ERROR = -502
+NGHTTP2_ERR_INVALID_STATE = -519
 NGHTTP2_ERR_HEADER_COMP = -523
 NGHTTP2_ERR_INSUFF_BUFSIZE = -525
 NGHTTP2_ERR_FATAL = -900
@@ -545,8 +546,13 @@ class HpackInflater:
             self.p = None
 
     def change_table_size(self, settings_max):
-        _check(self.L.nghttp2_amd_hd_inflate_change_table_size(self.p, settings_max),
-               "inflate_change_table_size")
+        """nghttp2_hd_inflate_change_table_size: returns 0, or
+        NGHTTP2_ERR_INVALID_STATE (nothing changed) after a block that failed
+        in the middle of a representation."""
+        rv = self.L.nghttp2_amd_hd_inflate_change_table_size(self.p, settings_max)
+        if rv != NGHTTP2_ERR_INVALID_STATE:
+            _check(rv, "inflate_change_table_size")
+        return rv
 
     def dynamic_table(self):
         """[(name, value)] of the dynamic table, most recent first."""

@@ -64,6 +64,7 @@ typedef struct {
   size_t cap, first, count;
   size_t size, max, settings_max, min_max;
   int expect_size, bad;
+  int mid_block; /* a block failed outside EXPECT_TABLE_SIZE: the state stays there (no end_headers) */
 } ohi;
 
 ohi *ohi_new(void) {
@@ -94,8 +95,12 @@ static void shrink(ohi *h) {
   while (h->size > h->max && h->count) evict_oldest(h);
 }
 
-/* lib/nghttp2_hd.c:1290-1322 */
-void ohi_change_table_size(ohi *h, size_t v) {
+/* lib/nghttp2_hd.c:1290-1322: NGHTTP2_ERR_INVALID_STATE (-519), and nothing
+ * changed, unless the state is INFLATE_START or EXPECT_TABLE_SIZE.  A failed
+ * block leaves the state where it failed (:2283-2287; the caller of a failed
+ * block does not call end_headers, lib/nghttp2_session.c:3556-3690). */
+int ohi_change_table_size(ohi *h, size_t v) {
+  if (h->mid_block) return -519;
   h->settings_max = v;
   if (h->max > v) {
     h->expect_size = 1;
@@ -103,6 +108,7 @@ void ohi_change_table_size(ohi *h, size_t v) {
     h->max = v;
     shrink(h);
   }
+  return 0;
 }
 
 /* newest first: k = 0 is dynamic index 62 */
@@ -146,6 +152,7 @@ static int add(ohi *h, const uint8_t *n, size_t nl, const uint8_t *v, size_t vl)
 
 size_t ohi_num_entries(const ohi *h) { return h->count; }
 size_t ohi_table_size(const ohi *h) { return h->size; }
+size_t ohi_table_max(const ohi *h) { return h->max; }
 void ohi_get_entry(const ohi *h, size_t k, const uint8_t **n, size_t *nl, const uint8_t **v, size_t *vl) {
   const ohi_entry *e = get_dyn(h, k);
   *n = e->nv;
@@ -238,7 +245,7 @@ long ohi_inflate_block(ohi *h, const uint8_t *b, size_t len, uint8_t *arena, siz
   int head = 1;
   while (r.pos < r.len) {
     const uint8_t c = r.b[r.pos];
-    if (h->expect_size && (c & 0xE0) != 0x20) goto fail;
+    if (h->expect_size && (c & 0xE0) != 0x20) goto fail_expect;
     if ((c & 0xE0) == 0x20) {
       if (!head) goto fail;
       uint32_t v;
@@ -296,9 +303,11 @@ long ohi_inflate_block(ohi *h, const uint8_t *b, size_t len, uint8_t *arena, siz
       if (add(h, arena + f[0], nl, arena + f[2], vl)) return -2;
     }
   }
-  if (h->expect_size) goto fail; /* lib/nghttp2_hd.c:2259-2266 */
+  if (h->expect_size) goto fail_expect; /* lib/nghttp2_hd.c:2259-2266 */
   return (long)*nvused;
 fail:
+  h->mid_block = 1;
+fail_expect: /* the state is still EXPECT_TABLE_SIZE (:1942-1949) */
   h->bad = 1;
   return OHI_HEADER_COMP;
 }

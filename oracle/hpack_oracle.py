@@ -17,6 +17,8 @@ Restates (citations are /root/reference paths):
 from . import oracle as O
 
 MAX_NV = 65536           # NGHTTP2_HD_MAX_NV
+INVALID_STATE = -519     # NGHTTP2_ERR_INVALID_STATE
+INSUFF_BUFSIZE = -525    # NGHTTP2_ERR_INSUFF_BUFSIZE
 ENTRY_OVERHEAD = 32      # NGHTTP2_HD_ENTRY_OVERHEAD
 DEFAULT_TABLE = 4096     # NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
 HEADER_COMP = -523
@@ -45,7 +47,10 @@ assert len(STATIC) == 61
 
 
 class _Fail(Exception):
-    pass
+    """expect: the block failed in NGHTTP2_HD_STATE_EXPECT_TABLE_SIZE."""
+
+    def __init__(self, expect=False):
+        self.expect = expect
 
 
 class Inflater:
@@ -57,15 +62,23 @@ class Inflater:
         self.min_max = 0xFFFFFFFF
         self.expect_size = False
         self.bad = False
+        # a block failed outside EXPECT_TABLE_SIZE: fail: (:2283-2287) leaves
+        # the state where it was, and the caller of a failed block does not
+        # call end_headers (lib/nghttp2_session.c:3556-3690)
+        self.mid_block = False
 
-    # lib/nghttp2_hd.c:1290-1322
+    # lib/nghttp2_hd.c:1290-1322: INVALID_STATE, and nothing changed, unless
+    # the state is INFLATE_START or EXPECT_TABLE_SIZE
     def change_table_size(self, v):
+        if self.mid_block:
+            return INVALID_STATE
         self.settings_max = v
         if self.max > v:
             self.expect_size = True
             self.min_max = v
             self.max = v
             self._shrink()
+        return 0
 
     def _shrink(self):
         while self.size > self.max and self.table:
@@ -96,8 +109,9 @@ class Inflater:
             return HEADER_COMP, fields
         try:
             self._inflate(bytes(block), fields)
-        except _Fail:
+        except _Fail as e:
             self.bad = True
+            self.mid_block = not e.expect
             return HEADER_COMP, fields
         return len(fields), fields
 
@@ -152,7 +166,7 @@ class Inflater:
         while pos[0] < len(b):
             c = b[pos[0]]
             if self.expect_size and (c & 0xE0) != 0x20:
-                raise _Fail()
+                raise _Fail(expect=True)
             if (c & 0xE0) == 0x20:
                 if not head:
                     raise _Fail()
@@ -185,7 +199,7 @@ class Inflater:
                 self._add(name, value)
             fields.append((name, value, NO_INDEX if no_index else 0))
         if self.expect_size:  # the block ended in EXPECT_TABLE_SIZE (:2259-2266)
-            raise _Fail()
+            raise _Fail(expect=True)
 
 
 def block_has_huffman(b):
@@ -260,6 +274,7 @@ class Deflater:
         self.deflate_max = max_deflate
         self.max = 4096
         self.notify = False
+        self.bad = False
         self.min_max = 0xFFFFFFFF
         if max_deflate < 4096:
             self.notify, self.max = True, max_deflate
@@ -282,15 +297,42 @@ class Deflater:
             self.table.insert(0, (n, v))
             self.size += room
 
+    @staticmethod
+    def bound(fields):
+        """nghttp2_hd_deflate_bound (:1596-1621)."""
+        return 12 + 12 * len(fields) + sum(len(f[0]) + len(f[1]) for f in fields)
+
     def deflate_block(self, fields):
+        rv, out = self.deflate_hd2(fields, None)
+        assert rv >= 0
+        return out
+
+    def deflate_hd2(self, fields, buflen):
+        """nghttp2_hd_deflate_hd2 (:1525-1555) into buflen bytes (None: no
+        limit), and nghttp2_hd_deflate_hd_vec2 over chunks of that total:
+        (rv, wire).  A representation that does not fit ends the block with
+        INSUFF_BUFSIZE after its table insertion (deflate_nv inserts, then
+        emits), and the deflater turns bad (:1512-1516)."""
+        if self.bad:
+            return HEADER_COMP, None
         out = bytearray()
+        for piece in self._pieces(fields):
+            out += piece
+            if buflen is not None and len(out) > buflen:
+                self.bad = True
+                return INSUFF_BUFSIZE, None
+        return len(out), bytes(out)
+
+    def _pieces(self, fields):
+        """The block's wire, one representation at a time."""
         if self.notify:
             mn = self.min_max
             self.notify, self.min_max = False, 0xFFFFFFFF
             if self.max > mn:
-                out += O.encode_length(mn, 5, 0x20)
-            out += O.encode_length(self.max, 5, 0x20)
+                yield O.encode_length(mn, 5, 0x20)
+            yield O.encode_length(self.max, 5, 0x20)
         for f in fields:
+            out = bytearray()
             n, v = bytes(f[0]), bytes(f[1])
             flags = f[2] if len(f) > 2 else 0
             token = _STATIC_TOKEN.get(n, -1)
@@ -321,7 +363,7 @@ class Deflater:
                             break
                         s += 1
             if exact:
-                out += O.encode_length(idx + 1, 7, 0x80)
+                yield O.encode_length(idx + 1, 7, 0x80)
                 continue
             if mode == _WITH:
                 self._add(n, v)
@@ -332,7 +374,7 @@ class Deflater:
             else:
                 out += O.encode_length(idx + 1, 6 if mode == _WITH else 4, first)
             out += O.emit_string(v)
-        return bytes(out)
+            yield bytes(out)
 
 
 # ---------------------------------------------------------------------------
@@ -381,7 +423,10 @@ def _clib():
         vp, sz = ctypes.c_void_p, ctypes.c_size_t
         L.ohi_new.restype = vp
         L.ohi_del.argtypes = [vp]
+        L.ohi_change_table_size.restype = ctypes.c_int
         L.ohi_change_table_size.argtypes = [vp, sz]
+        L.ohi_table_max.restype = sz
+        L.ohi_table_max.argtypes = [vp]
         L.ohi_num_entries.restype = sz
         L.ohi_num_entries.argtypes = [vp]
         L.ohi_table_size.restype = sz
@@ -412,7 +457,7 @@ class CInflater:
             self.p = None
 
     def change_table_size(self, v):
-        self.L.ohi_change_table_size(self.p, v)
+        return self.L.ohi_change_table_size(self.p, v)
 
     @property
     def table(self):
@@ -429,6 +474,9 @@ class CInflater:
 
     def table_size(self):
         return self.L.ohi_table_size(self.p)
+
+    def table_max(self):
+        return self.L.ohi_table_max(self.p)
 
     def inflate_block(self, block):
         import ctypes
