@@ -31,72 +31,17 @@
 // string -- a byte scan, no MFMA.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "hd_field_classes.h"
+#include "hd_host.h"
+#include "hd_string_walk.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 
 constexpr uint32_t CK_WG = 256;  // four waves, 64 strings each
 
 __constant__ hdcls::Table kClsTable = hdcls::kTable;
-
-// A wave's LDS accesses before this point are complete and visible to all of
-// its lanes after it (the hand-over between lanes of one wave through LDS,
-// no workgroup barrier).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Wave-wide maximum on DPP (row shifts within 16-lane rows, then row
-// broadcasts of lanes 15 and 31, as hd_huff.hip's scans): VALU only.  Lanes
-// whose DPP source lies outside the row read 0, the identity of an unsigned max.
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {  // uniform result
-  v = max(v, dpp0<0x111>(v));
-  v = max(v, dpp0<0x112>(v));
-  v = max(v, dpp0<0x114>(v));
-  v = max(v, dpp0<0x118>(v));
-  v = max(v, dpp0<0x142, 0xa>(v));
-  v = max(v, dpp0<0x143, 0xc>(v));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
-// OR of the class bytes [lo, hi) of a chunk's sixteen (0 <= lo, hi <= 16; an
-// empty range gives 0)
-__device__ __forceinline__ uint32_t or_bytes(const uint32_t w[4], uint32_t lo, uint32_t hi) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    // the bytes of dword k inside the range: [l, h) of its four
-    const int32_t l = max((int32_t)lo - 4 * k, 0), h = min((int32_t)hi - 4 * k, 4);
-    if (l < h) {
-      const uint32_t below_h = h == 4 ? 0xFFFFFFFFu : (1u << (8 * h)) - 1u;
-      r |= w[k] & below_h & ~((1u << (8 * l)) - 1u);
-    }
-  }
-  r |= r >> 16;
-  return (r | (r >> 8)) & 0xFFu;
-}
-__device__ __forceinline__ uint32_t byte_at(const uint32_t w[4], uint32_t i) {
-  const uint32_t d = i >> 2;
-  const uint32_t x = d == 0 ? w[0] : d == 1 ? w[1] : d == 2 ? w[2] : w[3];
-  return (x >> (8u * (i & 3u))) & 0xFFu;
-}
-__device__ __forceinline__ uint64_t ones64(uint32_t k) {  // the low k bits, k <= 64
-  return k >= 64u ? ~0ull : (1ull << k) - 1ull;
-}
 
 __global__ __launch_bounds__(CK_WG) void k_check_fields(const uint8_t *__restrict__ pool,
                                                         const uint32_t *__restrict__ off,
@@ -118,22 +63,10 @@ __global__ __launch_bounds__(CK_WG) void k_check_fields(const uint8_t *__restric
   const bool sl = lane < nstr;
   // string l in lane l: bytes [a, b); a string that is not examined is empty
   // here and reads nothing
-  uint32_t a = 0, b = 0;
-  bool valid = false;
-  if (sl) {
-    const uint32_t o0 = off[t0 + lane], o1 = off[t0 + lane + 1];
-    uint32_t l = o1 - o0;
-    valid = o0 <= o1;
-    if (len) {
-      const int32_t li = len[t0 + lane];
-      valid = valid && li >= 0 && (uint32_t)li <= l;
-      l = (uint32_t)li;
-    }
-    if (valid) {
-      a = o0;
-      b = o0 + l;
-    }
-  }
+  hdwalk::Range r = {0u, 0u, false};
+  if (sl) r = hdwalk::string_range(off, len, t0 + lane);
+  const uint32_t a = r.a, b = r.b;
+  const bool valid = r.valid;
   // the wave's span [A, Z): from its first examined string to the furthest end
   const uint32_t A = ~wave_max(valid ? ~a : 0u), Z = wave_max(b);
   const bool any = __ballot(valid) != 0ull;
@@ -232,10 +165,7 @@ int nghttp2_amd_hd_check_fields_batch(const uint8_t *pool, const uint32_t *off, 
   if (!pool || !off || !mask) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(k_check_fields, dim3((n + CK_WG - 1u) / CK_WG), dim3(CK_WG), 0, (hipStream_t)stream,
                      pool, off, len, n, mask);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  fprintf(stderr, "nghttp2_amd_hd: HIP error %s\n", hipGetErrorString(e));
-  return NGHTTP2_AMD_ERR_FATAL;
+  return hdhost::hip_rv(hipGetLastError());
 }
 
 uint8_t nghttp2_amd_hd_check_field(const uint8_t *s, size_t len) {

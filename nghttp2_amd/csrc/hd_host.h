@@ -1,7 +1,8 @@
 // hd_host.h -- what the host layers above the C ABI share (hd_inflate.cpp,
 // hd_deflate.cpp, hd_sharded.cpp): the HPACK static table with its lengths
-// computed at compile time, the HIP error report, and the growable device
-// and pinned host buffers the layers stage their batches in.
+// computed at compile time, the HIP error reports (hip_rv is the kernel
+// layers' own, the .hip files'), and the growable device and pinned host
+// buffers the layers stage their batches in.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "../../include/nghttp2_amd_hd.h"
 #include "hd_tokens.h"
 
 namespace hdhost {
@@ -65,6 +67,13 @@ inline bool hip_ok(hipError_t e, const char *layer, const char *what) {
   else
     fprintf(stderr, "nghttp2_amd_hd (%s): HIP error %s\n", layer, hipGetErrorString(e));
   return false;
+}
+// The C ABI's report of a launch or runtime call of the kernel layers (the
+// .hip files, which name no layer): 0, or the message and FATAL.
+inline int hip_rv(hipError_t e) {
+  if (e == hipSuccess) return 0;
+  fprintf(stderr, "nghttp2_amd_hd: HIP error %s\n", hipGetErrorString(e));
+  return NGHTTP2_AMD_ERR_FATAL;
 }
 inline size_t round16(size_t x) { return (x + 15u) & ~size_t(15); }
 // Buffers that grow and never shrink.  Their owner releases them explicitly: no

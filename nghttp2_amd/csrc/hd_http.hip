@@ -31,73 +31,18 @@
 // string -- a byte scan, no MFMA.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_host.h"
 #include "hd_http.h"
+#include "hd_string_walk.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 
 constexpr uint32_t HF_WG = 256;  // four waves, 64 strings each
 constexpr int NB = hdhttp::kBallots;
 
 __constant__ hdhttp::Table kHttpTable = hdhttp::kTable;
-
-// (the helpers below are hd_check.hip's: this file is its own translation
-// unit so that k_check_fields' code object stays as it is)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {  // uniform result
-  v = max(v, dpp0<0x111>(v));
-  v = max(v, dpp0<0x112>(v));
-  v = max(v, dpp0<0x114>(v));
-  v = max(v, dpp0<0x118>(v));
-  v = max(v, dpp0<0x142, 0xa>(v));
-  v = max(v, dpp0<0x143, 0xc>(v));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// OR of the class bytes [lo, hi) of a chunk's sixteen (an empty range gives 0)
-__device__ __forceinline__ uint32_t or_bytes(const uint32_t w[4], uint32_t lo, uint32_t hi) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int32_t l = max((int32_t)lo - 4 * k, 0), h = min((int32_t)hi - 4 * k, 4);
-    if (l < h) {
-      const uint32_t below_h = h == 4 ? 0xFFFFFFFFu : (1u << (8 * h)) - 1u;
-      r |= w[k] & below_h & ~((1u << (8 * l)) - 1u);
-    }
-  }
-  r |= r >> 16;
-  return (r | (r >> 8)) & 0xFFu;
-}
-__device__ __forceinline__ uint32_t byte_at(const uint32_t w[4], uint32_t i) {
-  const uint32_t d = i >> 2;
-  const uint32_t x = d == 0 ? w[0] : d == 1 ? w[1] : d == 2 ? w[2] : w[3];
-  return (x >> (8u * (i & 3u))) & 0xFFu;
-}
-// the first of the class bytes [lo, hi) of a chunk's sixteen with `bit` set, or 16
-__device__ __forceinline__ uint32_t first_with(const uint32_t w[4], uint32_t bit, uint32_t lo, uint32_t hi) {
-  uint32_t r = 16u;
-#pragma unroll
-  for (int i = 15; i >= 0; --i)
-    if ((uint32_t)i >= lo && (uint32_t)i < hi && ((w[i >> 2] >> (8 * (i & 3))) & bit)) r = (uint32_t)i;
-  return r;
-}
-__device__ __forceinline__ uint64_t ones64(uint32_t k) {  // the low k bits, k <= 64
-  return k >= 64u ? ~0ull : (1ull << k) - 1ull;
-}
 
 __global__ __launch_bounds__(HF_WG) void k_http_facts(const uint8_t *__restrict__ pool,
                                                       const uint32_t *__restrict__ off,
@@ -118,22 +63,10 @@ __global__ __launch_bounds__(HF_WG) void k_http_facts(const uint8_t *__restrict_
   const bool sl = lane < nstr;
   // string l in lane l: bytes [a, b); a string that is not examined is empty
   // here and reads nothing
-  uint32_t a = 0, b = 0;
-  bool valid = false;
-  if (sl) {
-    const uint32_t o0 = off[t0 + lane], o1 = off[t0 + lane + 1];
-    uint32_t l = o1 - o0;
-    valid = o0 <= o1;
-    if (len) {
-      const int32_t li = len[t0 + lane];
-      valid = valid && li >= 0 && (uint32_t)li <= l;
-      l = (uint32_t)li;
-    }
-    if (valid) {
-      a = o0;
-      b = o0 + l;
-    }
-  }
+  hdwalk::Range r = {0u, 0u, false};
+  if (sl) r = hdwalk::string_range(off, len, t0 + lane);
+  const uint32_t a = r.a, b = r.b;
+  const bool valid = r.valid;
   // the wave's span [A, Z): from its first examined string to the furthest end
   const uint32_t A = ~wave_max(valid ? ~a : 0u), Z = wave_max(b);
   const bool any = __ballot(valid) != 0ull;
@@ -263,10 +196,7 @@ int nghttp2_amd_hd_http_facts_batch(const uint8_t *pool, const uint32_t *off, co
   if (!pool || !off || !facts || !number) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(k_http_facts, dim3((n + HF_WG - 1u) / HF_WG), dim3(HF_WG), 0, (hipStream_t)stream, pool, off,
                      len, n, facts, number);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  fprintf(stderr, "nghttp2_amd_hd: HIP error %s\n", hipGetErrorString(e));
-  return NGHTTP2_AMD_ERR_FATAL;
+  return hdhost::hip_rv(hipGetLastError());
 }
 
 uint32_t nghttp2_amd_hd_http_facts(const uint8_t *s, size_t len, int64_t *number) {

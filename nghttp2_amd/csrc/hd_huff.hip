@@ -48,6 +48,8 @@
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "../../include/nghttp2_amd_hd_testing.h"
+#include "hd_host.h"
+#include "hd_wave.h"
 
 namespace dev {
 #define HD_TBL static __device__
@@ -101,11 +103,7 @@ static __device__ uint32_t g_hd_bounds[64];
 // Wave-wide inclusive scans on DPP (row shifts within 16-lane rows, then
 // row broadcasts of lanes 15 and 31): VALU only, no LDS round trips.
 // Lanes whose DPP source lies outside the row read 0, the identity of
-// add / max / or over unsigned values.
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
-}
+// add / max / or over unsigned values (dpp0: hd_wave.h).
 #define WAVE_SCAN(v, OP)                                                        \
   do {                                                                          \
     v = OP(v, dpp0<0x111>(v));                                                  \
@@ -129,15 +127,6 @@ __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {  // uniform result
   WAVE_SCAN(v, op_or);
   return __builtin_amdgcn_readlane(v, 63);
-}
-
-// A wave's LDS accesses before this point are complete and visible to all of
-// its lanes after it (release fence, wave barrier, acquire fence): the
-// hand-over between lanes of one wave through LDS, no workgroup barrier.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // s_waitcnt takes its counters as one immediate whose layout is the device
@@ -224,13 +213,7 @@ struct ByteOut {
   }
 };
 
-// Address-space-explicit pointers, so LDS staging compiles to ds_* and
-// global output to global_* (never flat_*).
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+// (the LDS pointer types are hd_wave.h's)
 // byte-aligned views for unaligned global stores (gfx950 takes them whole)
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef u32x4 __attribute__((aligned(1))) u32x4u;
@@ -2738,11 +2721,7 @@ static uint32_t persistent_grid(uint32_t n) {
   return g < c ? g : c;
 }
 
-static int hip_rv(hipError_t e) {
-  if (e == hipSuccess) return 0;
-  fprintf(stderr, "nghttp2_amd_hd: HIP error %s\n", hipGetErrorString(e));
-  return NGHTTP2_AMD_ERR_FATAL;
-}
+using hdhost::hip_rv;
 
 #ifndef HD_PART_ENC
 template <class C>

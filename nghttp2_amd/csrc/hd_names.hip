@@ -17,18 +17,18 @@
 // a hash + length hit is verified with dword compares against the name's
 // bytes still in registers.  HBM traffic per
 // name: its bytes + 4 (offset) in, 8 out -- an HBM-bound byte scan, no MFMA.
-// k_name_tokens_len is the same walk over (pool, off, len): a decode's output
-// in place, which the inflater tokenises right behind the decode.
+// k_name_tokens<true> is the same walk over (pool, off, len): a decode's
+// output in place, which the inflater tokenises right behind the decode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_host.h"
+#include "hd_string_walk.h"
+#include "hd_wave.h"
 #include "hd_tokens.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 constexpr uint32_t NT_WG = 256;
 
@@ -49,51 +49,22 @@ __device__ __forceinline__ uint32_t hash_chunk(uint32_t h, uint4 c0, uint4 c1, u
   return h;
 }
 
-// token: probe by hash, verify length and bytes (the name's dwords
-// realigned from F -- the first 64 bytes from the aligned base below a --
-// with v_alignbyte; table names are dword aligned and zero padded).  Only
-// the len bytes from a enter the compare: the last dword is masked by len.
-// k_name_tokens_len's probe.  It is k_name_tokens' own, which stays written
-// out in that kernel: called from there, the same source gives that kernel
-// another register allocation (38 -> 40 VGPRs), and its code is to stay as
-// measured.
-__device__ __forceinline__ int32_t probe_token(const uint32_t (&F)[16], uint32_t a, uint32_t len, uint32_t h,
-                                               const lds_u32 *TH, const lds_u32 *TM, const lds_u32 *TN) {
-  int32_t tok = -1;
-  if (len <= 32u) {
-    const uint32_t qw = (a & 15u) >> 2, sh = a & 3u;
-    uint32_t G[9];
-#pragma unroll
-    for (uint32_t j = 0; j < 9u; ++j)
-      G[j] = qw == 0 ? F[j] : qw == 1 ? F[j + 1] : qw == 2 ? F[j + 2] : F[j + 3];
-    uint32_t nm[8];
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; ++i) {
-      uint32_t v = __builtin_amdgcn_alignbyte(G[i + 1], G[i], sh);
-      const uint32_t left = len > 4u * i ? len - 4u * i : 0u;
-      nm[i] = left >= 4u ? v : v & ((1u << (8u * left)) - 1u);
-    }
-    for (uint32_t slot = h & (hdtok::kSlots - 1u), k = 0; k < hdtok::kSlots;
-         ++k, slot = (slot + 1u) & (hdtok::kSlots - 1u)) {
-      const uint32_t m = TM[slot];
-      if (m == 0) break;
-      if (TH[slot] != h || hdtok::meta_len(m) != len) continue;
-      const lds_u32 *q = TN + (hdtok::meta_off(m) >> 2);
-      bool eq = true;
-#pragma unroll
-      for (uint32_t i = 0; i < 8u; ++i)
-        if (4u * i < len) eq = eq && nm[i] == q[i];
-      if (eq) {
-        tok = (int32_t)hdtok::meta_token(m);
-        break;
-      }
-    }
-  }
-  return tok;
-}
-
+// LEN false: name s is names[off[s] .. off[s + 1]), and `hash` is required.
+// LEN true: a length per name (`len`, optional) and an optional hash: name s
+// is names[off[s] .. off[s] + len[s]) -- decode_batch_auto's (dst, dst_off,
+// status), dense per task with gaps between tasks and negative lengths for
+// failed strings.  A name that is not examined (hdwalk::string_range) reads
+// nothing and gives NGHTTP2_AMD_TOKEN_INVALID, hash 0.  Without `hash` a
+// string longer than every token name gives -1 unread: the inflater runs this
+// over every decoded literal, values included, and a 60 KB value must not
+// cost its wave 2,000 chunk rounds.  A lane that leaves early is missed by
+// nothing: after the table staging the kernel has no wave-wide step.  No byte
+// outside [a, b) reaches the token or the hash: b bounds the hash range, the
+// prefetch condition and the compare's byte masks.
+template <bool LEN>
 __global__ __launch_bounds__(NT_WG) void k_name_tokens(const uint8_t *__restrict__ names,
-                                                       const uint32_t *__restrict__ off, uint32_t n,
+                                                       const uint32_t *__restrict__ off,
+                                                       const int32_t *__restrict__ len, uint32_t n,
                                                        int32_t *__restrict__ token,
                                                        uint32_t *__restrict__ hash) {
   __shared__ uint32_t th[hdtok::kSlots], tm[hdtok::kSlots];
@@ -108,7 +79,22 @@ __global__ __launch_bounds__(NT_WG) void k_name_tokens(const uint8_t *__restrict
   const lds_u32 *TH = (const lds_u32 *)th, *TM = (const lds_u32 *)tm, *TN = (const lds_u32 *)tn;
   const uint32_t s = blockIdx.x * NT_WG + threadIdx.x;
   if (s >= n) return;
-  const uint32_t a = off[s], b = off[s + 1], len = b - a;
+  uint32_t a, b;
+  if constexpr (LEN) {
+    const hdwalk::Range r = hdwalk::string_range(off, len, s);
+    if (!r.valid) {
+      token[s] = NGHTTP2_AMD_TOKEN_INVALID;
+      if (hash) hash[s] = 0u;
+      return;
+    }
+    if (!hash && r.b - r.a > hdtok::kMaxTokenLen) {
+      token[s] = NGHTTP2_AMD_TOKEN_NONE;
+      return;
+    }
+    a = r.a, b = r.b;
+  } else {
+    a = off[s], b = off[s + 1];
+  }
   // FNV-1a over 32-byte chunks from the 16-byte aligned base below the name,
   // the next chunk's loads issued before the current chunk is hashed.  The
   // first two chunks stay in registers (F) for the token compare: a name of
@@ -141,10 +127,13 @@ __global__ __launch_bounds__(NT_WG) void k_name_tokens(const uint8_t *__restrict
     c1 = n1;
   }
   // token: probe by hash, verify length and bytes (the name's dwords
-  // realigned from F with v_alignbyte; table names are dword aligned and
-  // zero padded)
+  // realigned from F -- the first 64 bytes from the aligned base below a --
+  // with v_alignbyte; table names are dword aligned and zero padded).  Only
+  // the l bytes from a enter the compare: the last dword is masked by l.
+  // (Written out here, not a function that takes F: DESIGN.md 2.9.)
+  const uint32_t l = b - a;
   int32_t tok = -1;
-  if (len <= 32u) {
+  if (l <= 32u) {
     const uint32_t qw = (a & 15u) >> 2, sh = a & 3u;
     uint32_t G[9];
 #pragma unroll
@@ -154,19 +143,19 @@ __global__ __launch_bounds__(NT_WG) void k_name_tokens(const uint8_t *__restrict
 #pragma unroll
     for (uint32_t i = 0; i < 8u; ++i) {
       uint32_t v = __builtin_amdgcn_alignbyte(G[i + 1], G[i], sh);
-      const uint32_t left = len > 4u * i ? len - 4u * i : 0u;
+      const uint32_t left = l > 4u * i ? l - 4u * i : 0u;
       nm[i] = left >= 4u ? v : v & ((1u << (8u * left)) - 1u);
     }
     for (uint32_t slot = h & (hdtok::kSlots - 1u), k = 0; k < hdtok::kSlots;
          ++k, slot = (slot + 1u) & (hdtok::kSlots - 1u)) {
       const uint32_t m = TM[slot];
       if (m == 0) break;
-      if (TH[slot] != h || hdtok::meta_len(m) != len) continue;
+      if (TH[slot] != h || hdtok::meta_len(m) != l) continue;
       const lds_u32 *q = TN + (hdtok::meta_off(m) >> 2);
       bool eq = true;
 #pragma unroll
       for (uint32_t i = 0; i < 8u; ++i)
-        if (4u * i < len) eq = eq && nm[i] == q[i];
+        if (4u * i < l) eq = eq && nm[i] == q[i];
       if (eq) {
         tok = (int32_t)hdtok::meta_token(m);
         break;
@@ -174,91 +163,7 @@ __global__ __launch_bounds__(NT_WG) void k_name_tokens(const uint8_t *__restrict
     }
   }
   token[s] = tok;
-  hash[s] = h;
-}
-
-// The same with a length per name (`len`, optional) and an optional hash:
-// name s is names[off[s] .. off[s] + len[s]) -- decode_batch_auto's (dst,
-// dst_off, status), dense per task with gaps between tasks and negative
-// lengths for failed strings.  A name that is not examined (a negative or
-// overrunning length, descending offsets) reads nothing and gives
-// NGHTTP2_AMD_TOKEN_INVALID, hash 0.  Without `hash` a string longer than
-// every token name gives -1 unread: the inflater runs this over every decoded
-// literal, values included, and a 60 KB value must not cost its wave 2,000
-// chunk rounds.  A lane that leaves early is missed by nothing: after the
-// table staging the kernel has no wave-wide step.  The walk is
-// k_name_tokens', with b = a + len in every place: the hash range, the
-// prefetch condition and the compare's byte masks, so no byte outside
-// [a, a + len) reaches the token or the hash.
-__global__ __launch_bounds__(NT_WG) void k_name_tokens_len(const uint8_t *__restrict__ names,
-                                                           const uint32_t *__restrict__ off,
-                                                           const int32_t *__restrict__ len, uint32_t n,
-                                                           int32_t *__restrict__ token,
-                                                           uint32_t *__restrict__ hash) {
-  __shared__ uint32_t th[hdtok::kSlots], tm[hdtok::kSlots];
-  __shared__ uint32_t tn[hdtok::kNameBytes / 4];
-  for (uint32_t i = threadIdx.x; i < hdtok::kSlots; i += NT_WG) {
-    th[i] = kTokTable.hash[i];
-    tm[i] = kTokTable.meta[i];
-  }
-  for (uint32_t i = threadIdx.x; i < hdtok::kNameBytes / 4; i += NT_WG)
-    tn[i] = reinterpret_cast<const uint32_t *>(kTokTable.names)[i];
-  __syncthreads();  // the only workgroup barrier
-  const lds_u32 *TH = (const lds_u32 *)th, *TM = (const lds_u32 *)tm, *TN = (const lds_u32 *)tn;
-  const uint32_t s = blockIdx.x * NT_WG + threadIdx.x;
-  if (s >= n) return;
-  // (the length's load first: issued behind the offsets' it would start only
-  // after they have arrived, a second memory latency per wave)
-  int32_t li = 0;
-  if (len) li = len[s];
-  const uint32_t a = off[s], o1 = off[s + 1];
-  // (a <= o1 first, so o1 - a cannot wrap; the length is compared with that
-  // room, never added to an offset before it is known to fit)
-  bool valid = a <= o1;
-  uint32_t l = o1 - a;
-  if (len) {
-    valid = valid && li >= 0 && (uint32_t)li <= l;
-    l = (uint32_t)li;
-  }
-  if (!valid) {
-    token[s] = NGHTTP2_AMD_TOKEN_INVALID;
-    if (hash) hash[s] = 0u;
-    return;
-  }
-  if (!hash && l > hdtok::kMaxTokenLen) {
-    token[s] = NGHTTP2_AMD_TOKEN_NONE;
-    return;
-  }
-  const uint32_t b = a + l;
-  const uint4 *g = reinterpret_cast<const uint4 *>(names);
-  uint32_t h = hdtok::kFnvBasis;
-  uint32_t cb = a & ~15u;
-  uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0, n0 = c0, n1 = c0;
-  if (a < b) {
-    c0 = g[cb >> 4];
-    c1 = g[(cb >> 4) + 1u];
-  }
-  if (cb + 32u < b) {
-    n0 = g[(cb >> 4) + 2u];
-    n1 = g[(cb >> 4) + 3u];
-  }
-  const uint32_t F[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w,
-                          n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
-  h = hash_chunk(h, c0, c1, cb, a, b);
-  cb += 32u;
-  c0 = n0;
-  c1 = n1;
-  for (; cb < b; cb += 32u) {
-    if (cb + 32u < b) {
-      n0 = g[(cb >> 4) + 2u];
-      n1 = g[(cb >> 4) + 3u];
-    }
-    h = hash_chunk(h, c0, c1, cb, a, b);
-    c0 = n0;
-    c1 = n1;
-  }
-  token[s] = probe_token(F, a, l, h, TH, TM, TN);
-  if (hash) hash[s] = h;
+  if (!LEN || hash) hash[s] = h;
 }
 
 }  // namespace
@@ -269,24 +174,18 @@ int nghttp2_amd_hd_name_tokens_batch(const uint8_t *names, const uint32_t *name_
                                      int32_t *token, uint32_t *hash, void *stream) {
   if (n == 0) return 0;
   if (!names || !name_off || !token || !hash) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_name_tokens, dim3((n + NT_WG - 1u) / NT_WG), dim3(NT_WG), 0,
-                     (hipStream_t)stream, names, name_off, n, token, hash);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  fprintf(stderr, "nghttp2_amd_hd: HIP error %s\n", hipGetErrorString(e));
-  return NGHTTP2_AMD_ERR_FATAL;
+  hipLaunchKernelGGL(k_name_tokens<false>, dim3((n + NT_WG - 1u) / NT_WG), dim3(NT_WG), 0, (hipStream_t)stream,
+                     names, name_off, (const int32_t *)nullptr, n, token, hash);
+  return hdhost::hip_rv(hipGetLastError());
 }
 
 int nghttp2_amd_hd_name_tokens_len_batch(const uint8_t *pool, const uint32_t *off, const int32_t *len,
                                          uint32_t n, int32_t *token, uint32_t *hash, void *stream) {
   if (n == 0) return 0;
   if (!pool || !off || !token) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_name_tokens_len, dim3((n + NT_WG - 1u) / NT_WG), dim3(NT_WG), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_name_tokens<true>, dim3((n + NT_WG - 1u) / NT_WG), dim3(NT_WG), 0, (hipStream_t)stream,
                      pool, off, len, n, token, hash);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  fprintf(stderr, "nghttp2_amd_hd: HIP error %s\n", hipGetErrorString(e));
-  return NGHTTP2_AMD_ERR_FATAL;
+  return hdhost::hip_rv(hipGetLastError());
 }
 
 int32_t nghttp2_amd_hd_lookup_token(const uint8_t *name, size_t namelen) {

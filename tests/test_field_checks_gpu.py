@@ -15,6 +15,7 @@ import pytest
 from nghttp2_amd import workloads as W
 from oracle import oracle as O
 from tests import field_checks_ref as R
+from tests.string_batches import lay_out
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,15 +36,7 @@ def run(codec, dev, strings, lead=b"", tail=b"", gap=None):
     off[0]), with `tail` after off[n] and the pool padded by the contract
     (zeros to align_up(off[n], 16) + 16 -- bytes that violate every table)."""
     import torch
-    off = np.zeros(len(strings) + 1, dtype=np.uint32)
-    off[0] = len(lead)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    off[1:] += len(lead)
-    body = lead + b"".join(strings) + tail
-    end = int(off[-1])
-    size = max((end + 15) // 16 * 16 + 16, len(body))
-    pool = np.zeros(size, dtype=np.uint8)
-    pool[:len(body)] = np.frombuffer(body, dtype=np.uint8)
+    pool, off = lay_out(strings, lead, tail)
     m = codec.check_fields(torch.from_numpy(pool).to(dev), torch.from_numpy(off.view(np.int32)).to(dev))
     return m.cpu().numpy()
 

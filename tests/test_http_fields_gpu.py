@@ -16,6 +16,7 @@ import pytest
 from nghttp2_amd import workloads as W
 from oracle import oracle as O
 from tests import http_fields_ref as R
+from tests.string_batches import lay_out
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,15 +35,7 @@ def run(codec, dev, strings, lead=b"", tail=b""):
     """The facts of `strings` laid back to back after `lead` (bytes before
     off[0]), with `tail` after off[n] and the pool padded by the contract."""
     import torch
-    off = np.zeros(len(strings) + 1, dtype=np.uint32)
-    off[0] = len(lead)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    off[1:] += len(lead)
-    body = lead + b"".join(strings) + tail
-    end = int(off[-1])
-    size = max((end + 15) // 16 * 16 + 16, len(body))
-    pool = np.zeros(size, dtype=np.uint8)
-    pool[:len(body)] = np.frombuffer(body, dtype=np.uint8)
+    pool, off = lay_out(strings, lead, tail)
     f, n = codec.http_facts_batch(torch.from_numpy(pool).to(dev), torch.from_numpy(off.view(np.int32)).to(dev))
     return f.cpu().numpy().view(np.uint32), n.cpu().numpy()
 

@@ -1,5 +1,5 @@
 """Name tokens from the inflate front-end with Huffman literals
-(nghttp2_amd_hd_inflate_blocks_fields: k_name_tokens_len queued behind the
+(nghttp2_amd_hd_inflate_blocks_fields: k_name_tokens<true> queued behind the
 batch's one decode, the tokens back in the status copy) on the GPU: a random
 multi-connection batch from the oracle's deflater with churning tables and
 corrupted blocks, every emitted field's token against the oracle's

@@ -1,4 +1,4 @@
-"""nghttp2_amd_hd_name_tokens_len_batch (k_name_tokens_len) on the GPU: name
+"""nghttp2_amd_hd_name_tokens_len_batch (k_name_tokens<true>) on the GPU: name
 tokens and FNV-1a hashes of strings given by (pool, off, len), bit-exact
 against the oracle's lookup_token / name_hash (oracle/hpack_oracle.py, pinned
 to the reference by tests/golden/name_tokens.json) on exactly the len bytes:
@@ -13,6 +13,7 @@ import nghttp2_amd
 from nghttp2_amd import workloads as W
 from oracle import hpack_oracle as H
 from oracle import oracle as O
+from tests.string_batches import padded, place
 
 pytestmark = pytest.mark.gpu
 
@@ -22,15 +23,6 @@ INVALID, NONE = nghttp2_amd.TOKEN_INVALID, nghttp2_amd.TOKEN_NONE
 
 def near_misses(name):
     return [name[:-1] + bytes([name[-1] ^ 1]), name[:-1], name + b"x", name.upper()]
-
-
-def padded(body, end=None):
-    """A pool holding `body`, zero padded to the contract's readable size for
-    strings that end at `end` (default: the body's end)."""
-    end = len(body) if end is None else end
-    pool = np.zeros(max((end + 15) // 16 * 16 + 16, 16), dtype=np.uint8)
-    pool[:len(body)] = np.frombuffer(bytes(body), dtype=np.uint8)[:pool.size]
-    return pool
 
 
 def tokens(codec, dev, pool, off, ln=None, want_hash=True):
@@ -53,29 +45,6 @@ def expect(codec, dev, pool, off, ln, strings):
            for i in range(len(strings)) if tok[i] != wt[i] or h[i] != wh[i]]
     assert not bad, bad[:6]
     assert np.array_equal(tokens(codec, dev, pool, off, ln, want_hash=False), np.array(wt, dtype=np.int32))
-
-
-SLOT = 96  # bytes per placed string: a multiple of 16, so off & 15 is the position's
-
-
-def place(items):
-    """items: (context bytes, at, start, length) -- the string is
-    context[start:start+length], placed at offset `at` of its own slot with the
-    rest of the context around it.  Returns (pool, off, len, strings)."""
-    n = len(items)
-    body = bytearray(SLOT * n + SLOT)
-    off = np.zeros(n + 1, dtype=np.uint32)
-    ln = np.zeros(n, dtype=np.int32)
-    strings = []
-    for i, (ctx, at, start, length) in enumerate(items):
-        base = SLOT * i + at - start  # the context's first byte
-        assert base >= SLOT * i and base + len(ctx) <= SLOT * (i + 1)
-        body[base:base + len(ctx)] = ctx
-        off[i] = SLOT * i + at
-        ln[i] = length
-        strings.append(bytes(ctx[start:start + length]))
-    off[n] = SLOT * n
-    return padded(body, SLOT * n), off, ln, strings
 
 
 def positions(length):

@@ -40,6 +40,10 @@
            2,048-block batch, alternated; with NGHTTP2_AMD_OTHER_LIB, that
            build's _fields against this build's in the same process.
 
+With NGHTTP2_AMD_OTHER_LIB the names, check, names_len and http_facts rows
+also make the same call from that build, alternated call by call with this
+build's on the same resident pools (the `other_*` figures).
+
 Prints one JSON object.  Not the bench.py contract (that is the hot path
 itself); the numbers go to DESIGN.md."""
 import json
@@ -50,6 +54,48 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def other_codec(dev):
+    """A codec whose string-scan calls (name_tokens, check_fields,
+    http_facts_batch) go to the build NGHTTP2_AMD_OTHER_LIB names; None without it."""
+    path = os.environ.get("NGHTTP2_AMD_OTHER_LIB")
+    if not path:
+        return None
+    import ctypes
+    import nghttp2_amd
+    c = nghttp2_amd.HuffmanBatchCodec(dev)
+    P = ctypes.CDLL(path)
+    for f in ("nghttp2_amd_hd_name_tokens_batch", "nghttp2_amd_hd_name_tokens_len_batch",
+              "nghttp2_amd_hd_check_fields_batch", "nghttp2_amd_hd_http_facts_batch"):
+        getattr(P, f).argtypes = getattr(c.L, f).argtypes
+    c.L = P
+    return c
+
+
+def alternate(calls, steps):
+    """`calls` (label -> function) alternated call by call on the current
+    stream, each call between two HIP events: best and median in us per label."""
+    import torch
+    s = torch.cuda.current_stream()
+    for _ in range(5):
+        for c in calls.values():
+            c()
+    ev = {k: [] for k in calls}
+    for _ in range(steps):
+        for k, c in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            c()
+            b.record(s)
+            ev[k].append((a, b))
+    torch.cuda.synchronize()
+    out = {}
+    for k, v in ev.items():
+        t = [a.elapsed_time(b) * 1e3 for a, b in v]
+        out[k + "_us_best"] = round(min(t), 2)
+        out[k + "_us_median"] = round(float(np.median(t)), 2)
+    return out
 
 
 def bench_emit(steps=20, cfg=2):
@@ -131,9 +177,12 @@ def bench_names(steps=50, long_frac=0.02):
     torch.cuda.synchronize()
     t = e0.elapsed_time(e1) / 1e3 / steps
     B = raw + 12 * n
+    other = other_codec(dev)
+    ab = alternate({"this": lambda: codec.name_tokens(names, no, token=tok, hash=h),
+                    "other": lambda: other.name_tokens(names, no, token=tok, hash=h)}, steps) if other else {}
     return {"names": n, "name_bytes": raw, "us_per_batch": round(t * 1e6, 2),
             "GBps_algorithmic": round(B / t / 1e9, 1), "hbm_frac": round(B / t / 8.0e12, 4),
-            "Gnames_per_s": round(n / t / 1e9, 3), "long_wave_frac": long_frac}
+            "Gnames_per_s": round(n / t / 1e9, 3), "long_wave_frac": long_frac, **ab}
 
 
 def bench_check(steps=30):
@@ -147,6 +196,7 @@ def bench_check(steps=30):
     import field_checks_ref as R
     dev = torch.device("cuda:0")
     codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    other = other_codec(dev)
     n = 1 << 20
     out = {}
     for label, (pool, off) in (("mixed_1M", W.gen_mixed_range(W.mixed_lengths(n), 0, n, threads=8)),
@@ -184,6 +234,9 @@ def bench_check(steps=30):
                       "count_GBps_R_plus_5N": round(B / te / 1e9, 1),
                       "check_us_median": round(float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e3, 2),
                       "encode_count_us_median": round(float(np.median([e[2].elapsed_time(e[3]) for e in ev])) * 1e3, 2)}
+        if other:
+            out[label].update(alternate({"this_check": lambda: codec.check_fields(src, so, mask=mask),
+                                         "other_check": lambda: other.check_fields(src, so, mask=mask)}, steps))
     return out
 
 
@@ -196,28 +249,11 @@ def bench_names_len(steps=30):
     from oracle import hpack_oracle as H
     dev = torch.device("cuda:0")
     codec = nghttp2_amd.HuffmanBatchCodec(dev)
-    s = torch.cuda.current_stream()
     n = 1 << 20
+    other = other_codec(dev)
 
     def timed(calls):
-        for _ in range(5):
-            for c in calls.values():
-                c()
-        ev = {k: [] for k in calls}
-        for _ in range(steps):
-            for k, c in calls.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record(s)
-                c()
-                b.record(s)
-                ev[k].append((a, b))
-        torch.cuda.synchronize()
-        out = {}
-        for k, v in ev.items():
-            t = [a.elapsed_time(b) * 1e3 for a, b in v]
-            out[k + "_us_best"] = round(min(t), 2)
-            out[k + "_us_median"] = round(float(np.median(t)), 2)
-        return out
+        return alternate(calls, steps)
 
     pool, off = W.gen_names(n)
     raw = int(off[-1])
@@ -235,7 +271,11 @@ def bench_names_len(steps=30):
     rows = {"names_1M": {"names": n, "name_bytes": raw, **timed({
         "old": lambda: codec.name_tokens(names, no, token=tok, hash=h),
         "len_hash": lambda: codec.name_tokens(names, no, token=tok2, hash=h2, len=ln),
-        "len_nohash": lambda: codec.name_tokens(names, no, token=tok3, len=ln, want_hash=False)})}}
+        "len_nohash": lambda: codec.name_tokens(names, no, token=tok3, len=ln, want_hash=False),
+        **({"other_old": lambda: other.name_tokens(names, no, token=tok, hash=h),
+            "other_len_hash": lambda: other.name_tokens(names, no, token=tok2, hash=h2, len=ln),
+            "other_len_nohash": lambda: other.name_tokens(names, no, token=tok3, len=ln, want_hash=False)}
+           if other else {})})}}
     r = rows["names_1M"]
     r["len_hash_over_old_best"] = round(r["len_hash_us_best"] / r["old_us_best"], 3)
     r["len_hash_over_old_median"] = round(r["len_hash_us_median"] / r["old_us_median"], 3)
@@ -251,7 +291,11 @@ def bench_names_len(steps=30):
     rows["mixed_values_1M"] = {"strings": n, "raw_bytes": raw,
                                "strings_up_to_max_token_len": int((ln <= 27).sum().item()), **timed({
                                    "len_nohash": lambda: codec.name_tokens(src, so, token=tv, len=ln, want_hash=False),
-                                   "len_hash": lambda: codec.name_tokens(src, so, token=tvh, hash=hv, len=ln)})}
+                                   "len_hash": lambda: codec.name_tokens(src, so, token=tvh, hash=hv, len=ln),
+                                   **({"other_len_nohash": lambda: other.name_tokens(src, so, token=tv, len=ln,
+                                                                                     want_hash=False),
+                                       "other_len_hash": lambda: other.name_tokens(src, so, token=tvh, hash=hv,
+                                                                                   len=ln)} if other else {})})}
     return rows
 
 
@@ -352,6 +396,7 @@ def bench_http_facts(steps=30):
     from tests import http_fields_ref as R
     dev = torch.device("cuda:0")
     codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    other = other_codec(dev)
     n = 1 << 20
     out = {}
     # a pool a peer could send: 4,096 numbers of 16 KiB, all '0' but a last digit
@@ -395,6 +440,10 @@ def bench_http_facts(steps=30):
                       "check_GBps_R_plus_5N": round((raw + 5 * n) / tc / 1e9, 1),
                       "http_facts_us_median": round(float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e3, 2),
                       "check_us_median": round(float(np.median([e[2].elapsed_time(e[3]) for e in ev])) * 1e3, 2)}
+        if other:
+            out[label].update(alternate(
+                {"this_http_facts": lambda: codec.http_facts_batch(src, so, facts=facts, number=number),
+                 "other_http_facts": lambda: other.http_facts_batch(src, so, facts=facts, number=number)}, steps))
     return out
 
 
