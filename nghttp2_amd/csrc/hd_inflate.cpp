@@ -48,23 +48,42 @@ const uint32_t kDefaultTable = 4096;   // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
 // Insertion and eviction allocate nothing once the rings have grown to the
 // connection's working size; a ring that cannot place an entry is compacted
 // into one twice as large.
-// An entry also carries the NGHTTP2_AMD_CHECK_* masks of its name and value
-// (kUnchecked until a checked call computes them: at insertion, or at the
-// first reference to an entry that an unchecked call inserted), so an indexed
-// field costs a checked call no byte scan.  The name's token (lookup_token)
-// travels the same way: kTokUnknown until a tokened call sets it, and so do the
-// value's HTTP facts and number (hd_http.h): kFactUnknown until an _http call.
+// An entry also carries what is known of its bytes, an Ann: filled at
+// insertion with what the inserting call computed, and at the first reference
+// by a call that wants more (entry_ann), so an indexed field costs an annotated
+// call no byte scan.
 const uint8_t kUnchecked = NGHTTP2_AMD_CHECK_INVALID;
 const int8_t kTokUnknown = -3;  // (below NGHTTP2_AMD_TOKEN_INVALID; a token is -1..67)
 const uint32_t kFactUnknown = NGHTTP2_AMD_HTTP_FACT_INVALID;
+// Which annotations a call wants: the check masks (a checked call), the name
+// tokens (a tokened call), the HTTP verdicts (an _http call, which needs the
+// other two as well).
+struct Want {
+  bool checks, tokens, http;
+  constexpr Want(bool c, bool t, bool h) : checks(c || h), tokens(t || h), http(h) {}
+  bool any() const { return checks || tokens; }
+};
+// The annotations of one field; by default nothing is known.
+struct Ann {
+  uint8_t cn = kUnchecked, cv = kUnchecked;  // the NGHTTP2_AMD_CHECK_* masks of name and value
+  int8_t tk = kTokUnknown;                   // the name's token (lookup_token)
+  uint32_t vf = kFactUnknown;                // the value's HTTP facts and number (hd_http.h)
+  int64_t vn = -1;
+  // the members w asks for that are not known yet, from the bytes
+  void fill_name(const uint8_t *n, size_t nl, Want w) {
+    if (w.checks && cn == kUnchecked) cn = hdcls::check_field(n, nl);
+    if (w.tokens && tk == kTokUnknown) tk = (int8_t)hdtok::lookup_token(n, nl);
+  }
+  void fill_value(const uint8_t *v, size_t vl, Want w) {
+    if (w.checks && cv == kUnchecked) cv = hdcls::check_field(v, vl);
+    if (w.http && vf == kFactUnknown) vf = hdhttp::http_facts(v, vl, &vn);
+  }
+};
 struct DynTable {
   struct Ent {
     size_t off;
     uint32_t nl, vl;
-    uint8_t cn = kUnchecked, cv = kUnchecked;
-    int8_t tk = kTokUnknown;
-    uint32_t vf = kFactUnknown;  // the value's facts and number
-    int64_t vn = -1;
+    Ann ann;
   };
   std::vector<Ent> ents;   // ring, capacity a power of two
   size_t e_first = 0;      // oldest entry
@@ -111,8 +130,7 @@ struct DynTable {
     buf.swap(nb);
   }
   // n / v must not point into this table (the caller passes copies)
-  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk,
-            uint32_t vf, int64_t vn) {
+  void push(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, const Ann &a) {
     if (count == ents.size()) {  // grow the descriptor ring, oldest first
       std::vector<Ent> ne(ents.empty() ? 16 : 2 * ents.size());
       for (size_t k = 0; k < count; ++k) ne[k] = ents[(e_first + k) & (ents.size() - 1)];
@@ -126,10 +144,11 @@ struct DynTable {
     }
     if (nl) memcpy(buf.data() + at, n, nl);
     if (vl) memcpy(buf.data() + at + nl, v, vl);
-    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, cn, cv, tk, vf, vn};
+    ents[(e_first + count) & (ents.size() - 1)] = Ent{at, (uint32_t)nl, (uint32_t)vl, a};
     ++count;
   }
 };
+static_assert(sizeof(DynTable::Ent) == 32, "the replay is sensitive to the descriptor's size");
 
 }  // namespace
 
@@ -161,15 +180,12 @@ struct nghttp2_amd_hd_inflater {
   // insert it unless it is larger than the whole table.  n / v are copies
   // outside the table (the caller's emitted field), so a name taken from an
   // entry that this insertion evicts stays valid, as in the reference.
-  // cn / cv: the field's check masks (kUnchecked from an unchecked call);
-  // tk: its name's token (kTokUnknown from a call without tokens); vf / vn:
-  // its value's HTTP facts (kFactUnknown from a call that is not _http).
-  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, uint8_t cn, uint8_t cv, int8_t tk,
-           uint32_t vf, int64_t vn) {
+  // a: what the inserting call knows of the field.
+  void add(const uint8_t *n, size_t nl, const uint8_t *v, size_t vl, const Ann &a) {
     const size_t room = nl + vl + kEntryOverhead;
     while (bufsize + room > bufsize_max && table.count) evict_oldest();
     if (room > bufsize_max) return;
-    table.push(n, nl, v, vl, cn, cv, tk, vf, vn);
+    table.push(n, nl, v, vl, a);
     bufsize += room;
     max_nl = std::max(max_nl, nl);
     max_vl = std::max(max_vl, vl);
@@ -185,70 +201,28 @@ struct nghttp2_amd_hd_inflater {
     *v = (const char *)table.value(e);
     *vl = e.vl;
   }
-  // the check masks of entry idx (as entry()): the static table's are computed
-  // once per process, a dynamic entry's are in its descriptor
-  void entry_checks(size_t idx, uint8_t *cn, uint8_t *cv) {
+  // the annotations of entry idx (as entry()) that w asks for: the static
+  // table's are all computed once per process; a dynamic entry's are in its
+  // descriptor, where this fills in what w asks for and no earlier call has
+  const Ann &entry_ann(size_t idx, Want w) {
     if (idx < kStaticLen) {
-      struct Masks {
-        uint8_t m[kStaticLen][2];
+      struct Anns {
+        Ann a[kStaticLen];
       };
-      static const Masks st = [] {
-        Masks t;
-        for (uint32_t i = 0; i < kStaticLen; ++i)
-          for (int w = 0; w < 2; ++w)
-            t.m[i][w] = hdcls::check_field((const uint8_t *)kStatic[i][w], kStaticLens.len[i][w]);
+      static const Anns st = [] {
+        Anns t;
+        for (uint32_t i = 0; i < kStaticLen; ++i) {
+          t.a[i].fill_name((const uint8_t *)kStatic[i][0], kStaticLens.len[i][0], Want(true, true, true));
+          t.a[i].fill_value((const uint8_t *)kStatic[i][1], kStaticLens.len[i][1], Want(true, true, true));
+        }
         return t;
       }();
-      *cn = st.m[idx][0];
-      *cv = st.m[idx][1];
-      return;
+      return st.a[idx];
     }
     DynTable::Ent &e = table.newest(idx - kStaticLen);
-    if (e.cn == kUnchecked) e.cn = hdcls::check_field(table.name(e), e.nl);
-    if (e.cv == kUnchecked) e.cv = hdcls::check_field(table.value(e), e.vl);
-    *cn = e.cn;
-    *cv = e.cv;
-  }
-  // the token of entry idx's name (as entry()): the static table's are looked
-  // up once per process, a dynamic entry's is in its descriptor
-  int8_t entry_token(size_t idx) {
-    if (idx < kStaticLen) {
-      struct Tokens {
-        int8_t t[kStaticLen];
-      };
-      static const Tokens st = [] {
-        Tokens t;
-        for (uint32_t i = 0; i < kStaticLen; ++i)
-          t.t[i] = (int8_t)hdtok::lookup_token((const uint8_t *)kStatic[i][0], kStaticLens.len[i][0]);
-        return t;
-      }();
-      return st.t[idx];
-    }
-    DynTable::Ent &e = table.newest(idx - kStaticLen);
-    if (e.tk == kTokUnknown) e.tk = (int8_t)hdtok::lookup_token(table.name(e), e.nl);
-    return e.tk;
-  }
-  // the HTTP facts and number of entry idx's value (as entry()), from the same
-  // two places
-  uint32_t entry_facts(size_t idx, int64_t *vn) {
-    if (idx < kStaticLen) {
-      struct Facts {
-        uint32_t f[kStaticLen];
-        int64_t n[kStaticLen];
-      };
-      static const Facts st = [] {
-        Facts t;
-        for (uint32_t i = 0; i < kStaticLen; ++i)
-          t.f[i] = hdhttp::http_facts((const uint8_t *)kStatic[i][1], kStaticLens.len[i][1], &t.n[i]);
-        return t;
-      }();
-      *vn = st.n[idx];
-      return st.f[idx];
-    }
-    DynTable::Ent &e = table.newest(idx - kStaticLen);
-    if (e.vf == kFactUnknown) e.vf = hdhttp::http_facts(table.value(e), e.vl, &e.vn);
-    *vn = e.vn;
-    return e.vf;
+    e.ann.fill_name(table.name(e), e.nl, w);
+    e.ann.fill_value(table.value(e), e.vl, w);
+    return e.ann;
   }
 };
 
@@ -294,14 +268,42 @@ struct alignas(128) Block {  // (aligned as BlockOut)
   uint64_t lit_name = 0, lit_val = 0;
 };
 
-// One block's emitted fields: name\0value\0 runs in `bytes`.
+// One emitted field: its name\0value\0 run's place in the bytes it was written
+// to, and what of its annotations the caller may have asked for.
 struct Rec {
   uint32_t name_off, name_len, value_off, value_len;
   uint8_t flags;
   uint8_t cn, cv;  // the check masks of name and value (a checked call)
   int8_t tk;       // the name's token (a tokened call)
   int32_t vd;      // the field's HTTP verdict (an _http call)
+  Rec(size_t at, size_t nl, size_t vl, uint8_t fl, const Ann &a, int32_t verdict)
+      : name_off((uint32_t)at), name_len((uint32_t)nl), value_off((uint32_t)(at + nl + 1)), value_len((uint32_t)vl),
+        flags(fl), cn(a.cn), cv(a.cv), tk(a.tk), vd(verdict) {}
 };
+static_assert(sizeof(Rec) == 24, "the replay is sensitive to the record's size");
+// The caller's per-field arrays: the fields and their bytes, and the masks,
+// tokens and verdicts of the calls that ask for them (else nullptr).
+struct FieldOut {
+  nghttp2_amd_hd_nv *nva;
+  uint8_t *arena;
+  uint8_t *checks;    // two masks per field
+  int32_t *tokens;    // a token per field
+  int32_t *verdicts;  // a verdict per field
+  // field k of the call: r of block `block`, whose bytes are at arena + base
+  void put(size_t k, uint32_t block, uint32_t base, const Rec &r) const {
+    nva[k] = nghttp2_amd_hd_nv{block, base + r.name_off, r.name_len, base + r.value_off, r.value_len, r.flags};
+    if (checks) checks[2 * k] = r.cn, checks[2 * k + 1] = r.cv;
+    if (tokens) tokens[k] = r.tk;
+    if (verdicts) verdicts[k] = r.vd;
+  }
+};
+// a field's name\0value\0 run at d, NUL-terminated like the reference's rcbufs (:2112, :2201)
+void put_bytes(uint8_t *d, const char *n, size_t nl, const char *v, size_t vl) {
+  if (nl) memcpy(d, n, nl);
+  d[nl] = 0;
+  if (vl) memcpy(d + nl + 1, v, vl);
+  d[nl + 1 + vl] = 0;
+}
 // A growable byte buffer written through a raw pointer (no per-append
 // capacity check or zero fill): a block's name\0value\0 runs.
 struct ByteBuf {
@@ -424,18 +426,24 @@ struct LitSrc {
     *n = (size_t)s;
     return true;
   }
-  // the check mask of a literal get() returned: a raw one is scanned here (on
-  // the replay's thread), a Huffman one was scanned behind its decode
-  uint8_t check(const Lit &l) const { return l.huff < 0 ? hdcls::check_field(l.p, l.len) : chk[l.huff]; }
-  // the token of a name literal get() returned, from the same two places
-  int8_t token(const Lit &l) const {
-    return (int8_t)(l.huff < 0 ? hdtok::lookup_token(l.p, l.len) : tok[l.huff]);
-  }
-  // the HTTP facts and number of a value literal get() returned, likewise
-  uint32_t facts(const Lit &l, int64_t *vn) const {
-    if (l.huff < 0) return hdhttp::http_facts(l.p, l.len, vn);
-    *vn = num[l.huff];
-    return fct[l.huff];
+  // what w asks for of a field whose value literal, and name literal unless
+  // the name is an entry's (nullptr), get() returned: a raw literal is scanned
+  // here (on the replay's thread), a Huffman one was scanned behind its decode
+  Ann ann(const Lit *name, const Lit &val, Want w) const {
+    Ann a;
+    if (name && name->huff < 0) {
+      a.fill_name(name->p, name->len, w);
+    } else if (name) {
+      if (w.checks) a.cn = chk[name->huff];
+      if (w.tokens) a.tk = (int8_t)tok[name->huff];
+    }
+    if (val.huff < 0) {
+      a.fill_value(val.p, val.len, w);
+    } else {
+      if (w.checks) a.cv = chk[val.huff];
+      if (w.http) a.vf = fct[val.huff], a.vn = num[val.huff];
+    }
+    return a;
   }
 };
 
@@ -474,24 +482,9 @@ struct BlockSink {
     out.recs.clear();
     out.bytes.clear();
   }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk,
-            int32_t vd) {
-    Rec r;
-    r.flags = flags;
-    r.vd = vd;
-    r.cn = cn;
-    r.cv = cv;
-    r.tk = tk;
-    r.name_off = (uint32_t)out.bytes.size();
-    r.name_len = (uint32_t)nl;
-    r.value_off = r.name_off + (uint32_t)nl + 1u;
-    r.value_len = (uint32_t)vl;
-    uint8_t *d = out.bytes.room(nl + vl + 2);
-    if (nl) memcpy(d, n, nl);
-    d[nl] = 0;  // NUL-terminated like the reference's rcbufs (:2112, :2201)
-    if (vl) memcpy(d + nl + 1, v, vl);
-    d[nl + 1 + vl] = 0;
-    out.recs.push_back(r);
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, const Ann &a, int32_t vd) {
+    out.recs.emplace_back(out.bytes.size(), nl, vl, flags, a, vd);
+    put_bytes(out.bytes.room(nl + vl + 2), n, nl, v, vl);
   }
   // the field just emitted (the table copies it from here)
   const uint8_t *last_name() const { return (const uint8_t *)out.bytes.data() + out.recs.back().name_off; }
@@ -500,39 +493,18 @@ struct BlockSink {
   int32_t count() const { return (int32_t)out.recs.size(); }
 };
 struct DirectSink {
-  uint8_t *arena;
-  nghttp2_amd_hd_nv *nva;
+  const FieldOut &fo;
   int32_t *status;
-  uint8_t *checks;  // the caller's nv_checks, or nullptr
-  int32_t *tokens;  // the caller's nv_tokens, or nullptr
-  int32_t *verdicts;  // the caller's nv_verdicts, or nullptr
   size_t ar = 0, nv = 0, nv0 = 0;
   uint32_t block = 0;
   void begin() { nv0 = nv; }
-  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, uint8_t cn, uint8_t cv, int8_t tk,
-            int32_t vd) {
-    if (verdicts) verdicts[nv] = vd;
-    if (checks) {
-      checks[2 * nv] = cn;
-      checks[2 * nv + 1] = cv;
-    }
-    if (tokens) tokens[nv] = tk;
-    nghttp2_amd_hd_nv &d = nva[nv++];
-    d.block = block;
-    d.flags = flags;
-    d.name_off = (uint32_t)ar;
-    d.name_len = (uint32_t)nl;
-    if (nl) memcpy(arena + ar, n, nl);
-    arena[ar + nl] = 0;
-    ar += nl + 1;
-    d.value_off = (uint32_t)ar;
-    d.value_len = (uint32_t)vl;
-    if (vl) memcpy(arena + ar, v, vl);
-    arena[ar + vl] = 0;
-    ar += vl + 1;
+  void emit(const char *n, size_t nl, const char *v, size_t vl, uint8_t flags, const Ann &a, int32_t vd) {
+    fo.put(nv++, block, 0, Rec(ar, nl, vl, flags, a, vd));
+    put_bytes(fo.arena + ar, n, nl, v, vl);
+    ar += nl + vl + 2;
   }
-  const uint8_t *last_name() const { return arena + nva[nv - 1].name_off; }
-  const uint8_t *last_value() const { return arena + nva[nv - 1].value_off; }
+  const uint8_t *last_name() const { return fo.arena + fo.nva[nv - 1].name_off; }
+  const uint8_t *last_value() const { return fo.arena + fo.nva[nv - 1].value_off; }
   void finish(int32_t st) { status[block] = st; }
   int32_t count() const { return (int32_t)(nv - nv0); }
 };
@@ -547,9 +519,9 @@ struct HttpRun {
   nghttp2_amd_hd_http_state st;
   bool stopped = false;
   int32_t result = 0;
-  int32_t step(const char *n, size_t nl, size_t vl, int8_t tk, uint8_t cn, uint8_t cv, uint32_t vf, int64_t vn) {
+  int32_t step(const char *n, size_t nl, size_t vl, const Ann &a) {
     if (stopped) return NGHTTP2_AMD_HTTP_NOT_EXAMINED;
-    const int rv = hdhttp::on_header(&st, mode, hdhttp::Field{(const uint8_t *)n, nl, vl, tk, cn, cv, vf, vn});
+    const int rv = hdhttp::on_header(&st, mode, hdhttp::Field{(const uint8_t *)n, nl, vl, a.tk, a.cn, a.cv, a.vf, a.vn});
     if (rv == NGHTTP2_AMD_ERR_HTTP_HEADER) {
       stopped = true;
       result = rv;
@@ -565,12 +537,11 @@ struct HttpRun {
   }
 };
 
-// chk: a checked call -- every emitted name and value with its check mask.
-// tok: a tokened call -- every emitted field with its name's token.
-// http: an _http call (chk and tok are set) -- every emitted field with its
-// verdict, the block's state and result in *http.
+// want: the annotations every emitted field carries.  http: an _http call
+// (want.http) -- every emitted field with its verdict, the block's state and
+// result in *http; else nullptr.
 template <class Sink>
-void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, bool chk, bool tok, HttpRun *http,
+void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls, Want want, HttpRun *http,
                   Sink &out) {
   out.begin();
   bool ok = !inf->bad;
@@ -595,33 +566,23 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     head = false;
     const char *n, *v;
     size_t nl, vl;
-    uint8_t cn = kUnchecked, cv = kUnchecked;
-    int8_t tk = kTokUnknown;
-    uint32_t vf = kFactUnknown;
-    int64_t vn = -1;
-    int32_t vd = 0;
     if (op.kind == Op::INDEXED) {  // hd_inflate_commit_indexed
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
         break;
       }
       inf->entry(op.value - 1, &n, &nl, &v, &vl);
-      if (chk) inf->entry_checks(op.value - 1, &cn, &cv);
-      if (tok) tk = inf->entry_token(op.value - 1);
-      if (http) {
-        vf = inf->entry_facts(op.value - 1, &vn);
-        vd = http->step(n, nl, vl, tk, cn, cv, vf, vn);
-      }
-      out.emit(n, nl, v, vl, 0, cn, cv, tk, vd);
+      static const Ann kNone;
+      const Ann &a = want.any() ? inf->entry_ann(op.value - 1, want) : kNone;
+      out.emit(n, nl, v, vl, 0, a, http ? http->step(n, nl, vl, a) : 0);
       continue;
     }
+    const Ann *name_ann = nullptr;  // an indexed name's
     if (op.new_name) {  // hd_inflate_commit_newname
       if (!ls.get(op.name, &n, &nl)) {
         ok = false;
         break;
       }
-      if (chk) cn = ls.check(op.name);
-      if (tok) tk = ls.token(op.name);
     } else {  // hd_inflate_commit_indname
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
@@ -630,23 +591,18 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       const char *v0;
       size_t vl0;
       inf->entry(op.value - 1, &n, &nl, &v0, &vl0);
-      uint8_t cv0;
-      if (chk) inf->entry_checks(op.value - 1, &cn, &cv0);
-      if (tok) tk = inf->entry_token(op.value - 1);
+      if (want.any()) name_ann = &inf->entry_ann(op.value - 1, want);
     }
     if (!ls.get(op.val, &v, &vl)) {
       ok = false;
       break;
     }
-    if (chk) cv = ls.check(op.val);
+    Ann a = ls.ann(op.new_name ? &op.name : nullptr, op.val, want);
+    if (name_ann) a.cn = name_ann->cn, a.tk = name_ann->tk;
     const uint8_t flags = op.no_index ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
-    if (http) {
-      vf = ls.facts(op.val, &vn);
-      vd = http->step(n, nl, vl, tk, cn, cv, vf, vn);
-    }
-    out.emit(n, nl, v, vl, flags, cn, cv, tk, vd);
+    out.emit(n, nl, v, vl, flags, a, http ? http->step(n, nl, vl, a) : 0);
     if (op.index_required)  // the table copies the field just emitted
-      inf->add(out.last_name(), nl, out.last_value(), vl, cn, cv, tk, vf, vn);
+      inf->add(out.last_name(), nl, out.last_value(), vl, a);
   }
   // truncated or malformed wire after the parsed representations; and a
   // block that ends while a table size update is still expected
@@ -673,20 +629,15 @@ using nghttp2_amd_host::Phases;
 
 // The caller's output buffers.
 struct Dest {
-  nghttp2_amd_hd_nv *nva;
+  FieldOut fo;
   size_t nva_cap, *nva_used;
-  uint8_t *arena;
   size_t arena_cap, *arena_used;
   int32_t *block_status;
-  uint8_t *nv_checks;  // a checked call: two masks per field; else nullptr
-  int32_t *nv_tokens;  // a tokened call: a token per field; else nullptr
-  // an _http call (block_modes given): a mode per block, the streams' states
-  // in and out, a verdict per field and a result per block (either may be
-  // nullptr); else all nullptr
+  // an _http call: a mode per block, the streams' states in and out, and a
+  // result per block (may be nullptr); else all nullptr
   const uint8_t *block_modes;
   nghttp2_amd_hd_http_state *block_state;
-  int32_t *nv_verdicts, *block_http;
-  bool http() const { return block_modes != nullptr; }
+  int32_t *block_http;
   HttpRun run(uint32_t i) const { return HttpRun{block_modes[i], block_state[i]}; }
   void set_http(uint32_t i, const nghttp2_amd_hd_http_state &st, int32_t res) const {
     block_state[i] = st;
@@ -816,13 +767,44 @@ int zc_mode() {
 // words and the masks and come back in that copy too.  Values get a token as
 // names do (pass 1 numbers the literals without telling them apart); the
 // replay reads the names' only.
-// An _http call (checks and tokens are set) queues
-// nghttp2_amd_hd_http_facts_batch behind those two; the numbers, an int64 per
-// literal at the next 8-byte boundary behind the status words, and the facts,
-// a uint32 per literal behind them, come before the tokens and come back in
-// that copy as well.  Names get facts as values do; the replay reads the values' only.
-int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, bool http, void *stream, Phases &ph,
-                 LitSrc *ls) {
+// An _http call queues nghttp2_amd_hd_http_facts_batch behind those two; the
+// numbers, an int64 per literal at the next 8-byte boundary behind the status
+// words, and the facts, a uint32 per literal behind them, come before the
+// tokens and come back in that copy as well.  Names get facts as values do;
+// the replay reads the values' only.
+//
+// MetaLayout is that pool for nh Huffman literals, as byte offsets from its
+// base (the device's copy, the mapped pool and the host's pool alike):
+//   [offsets: nh + 1 uint32, in] [slots: nh + 1 uint32] [status: nh int32]
+//   [pad to 8] [numbers: nh int64] [facts: nh uint32]      -- an _http call
+//   [tokens: nh int32]                                      -- a tokened call
+//   [masks: nh bytes]                                       -- a checked call
+// What follows `slots` comes back: the slots in one copy, [status, end) in another.
+struct MetaLayout {
+  size_t words;  // the bytes of nh + 1 of them: the offsets section, and the slots section
+  size_t offsets = 0, slots, status, numbers, facts, tokens, masks, end;
+  size_t size;  // of the pool (sized as if the status section, too, had nh + 1 words)
+  constexpr MetaLayout(uint32_t nh, Want w)
+      : words(((size_t)nh + 1u) * sizeof(uint32_t)),
+        slots(words),
+        status(2u * words),
+        numbers(w.http ? (status + nh * sizeof(int32_t) + 7u) / 8u * 8u : status + nh * sizeof(int32_t)),
+        facts(numbers + (w.http ? nh * sizeof(int64_t) : 0u)),
+        tokens(facts + (w.http ? nh * sizeof(uint32_t) : 0u)),
+        masks(tokens + (w.tokens ? nh * sizeof(int32_t) : 0u)),
+        end(masks + (w.checks ? nh : 0u)),
+        size(end + sizeof(int32_t)) {}
+  template <class T>
+  static T *at(void *base, size_t off) {
+    return (T *)((uint8_t *)base + off);
+  }
+};
+// (the numbers are read and written as int64: 8-aligned for either parity of nh)
+static_assert(MetaLayout(1, Want(false, false, true)).numbers == 24 && MetaLayout(2, Want(false, false, true)).numbers == 32 &&
+                  MetaLayout(3, Want(false, false, true)).numbers % 8 == 0 && MetaLayout(3, Want(true, true, false)).masks == 56,
+              "the metadata pool's layout");
+
+int stage_decode(Engine &E, uint32_t nblocks, Want want, void *stream, Phases &ph, LitSrc *ls) {
   for (uint32_t i = 0; i < nblocks; ++i) {
     E.nhuff[i + 1] += E.nhuff[i];
     E.hbytes[i + 1] += E.hbytes[i];
@@ -841,22 +823,15 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, bool htt
   // (the check reads whole 16-byte chunks up to the last slot's end, and one
   // at it when every literal is empty; the token lookup reads at most one
   // chunk past the chunk a literal ends in)
-  const size_t out_alloc = out_bytes + (checks || tokens ? 16u : 0u);
-  // behind the status words: [pad to 8, numbers: nh int64, facts: nh uint32]
-  // [tokens: nh int32] [checks: nh bytes].  The status words end at byte
-  // 4 * (3 nh + 2) of the pool: a multiple of 8 when nh is even
-  const size_t tok_bytes = tokens ? nh * sizeof(int32_t) : 0u, chk_bytes = checks ? nh : 0u;
-  const size_t http_pad = http && (nh & 1u) ? 4u : 0u;
-  const size_t http_bytes = http ? http_pad + nh * (sizeof(int64_t) + sizeof(uint32_t)) : 0u;
-  const size_t slots = (size_t)nh + 1u,
-               meta = 3u * slots * sizeof(uint32_t) + http_bytes + tok_bytes + chk_bytes;
+  const size_t out_alloc = out_bytes + (want.any() ? 16u : 0u);
+  const MetaLayout ml(nh, want);
   // (the output pool is a D2H copy target unless the kernel writes it
   // through the mapping, mode 1; the input pools are mapped unless mode 0;
   // mode 2 needs no device copy of the input)
   if (nh && (!E.h_pool.reserve(in_bytes, kLayer, mode != 0) || !E.h_out.reserve(out_alloc, kLayer, zero_copy) ||
-             !E.h_meta.reserve(meta, kLayer, mode != 0) ||
+             !E.h_meta.reserve(ml.size, kLayer, mode != 0) ||
              (!zero_copy && ((mode == 0 && !E.d_in.reserve(in_bytes, kLayer)) ||
-                             !E.d_out.reserve(out_alloc, kLayer) || !E.d_meta.reserve(meta, kLayer)))))
+                             !E.d_out.reserve(out_alloc, kLayer) || !E.d_meta.reserve(ml.size, kLayer)))))
     return NGHTTP2_AMD_ERR_NOMEM;
   ph.mark("pools");
   number_and_copy(E, nblocks);
@@ -864,9 +839,9 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, bool htt
   *ls = LitSrc{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (!nh) return 0;
   hipStream_t st = (hipStream_t)stream;
-  uint32_t *const h_meta = E.h_meta.as<uint32_t>();
+  void *const h_meta = E.h_meta.p;
   memset(E.h_pool.as<uint8_t>() + hb, 0, in_bytes - hb);
-  memcpy(h_meta, E.hoff.data(), slots * sizeof(uint32_t));
+  memcpy(h_meta, E.hoff.data(), ml.words);
   // a failure after the first copy or launch is queued drains the stream
   // before returning: GPU work still in flight must not land in the pinned
   // pools after the next call has filled them
@@ -884,47 +859,35 @@ int stage_decode(Engine &E, uint32_t nblocks, bool checks, bool tokens, bool htt
   const uint8_t *src = mode != 0 ? (const uint8_t *)m_in : E.d_in.as<uint8_t>();
   const uint32_t *src_off = mode != 0 ? (const uint32_t *)m_meta : E.d_meta.as<uint32_t>();
   uint8_t *dst = zero_copy ? (uint8_t *)m_out : E.d_out.as<uint8_t>();
-  uint32_t *d_slot = (zero_copy ? (uint32_t *)m_meta : E.d_meta.as<uint32_t>()) + slots;
-  int32_t *d_st = (int32_t *)(d_slot + slots);
-  if (mode == 0 &&
-      (hipMemcpyAsync(E.d_in.p, E.h_pool.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-       hipMemcpyAsync(E.d_meta.p, h_meta, slots * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess))
+  void *const d_meta = zero_copy ? m_meta : E.d_meta.p;  // where the kernels write
+  uint32_t *d_slot = ml.at<uint32_t>(d_meta, ml.slots);
+  int32_t *d_st = ml.at<int32_t>(d_meta, ml.status);
+  if (mode == 0 && (hipMemcpyAsync(E.d_in.p, E.h_pool.p, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                    hipMemcpyAsync(E.d_meta.p, h_meta, ml.words, hipMemcpyHostToDevice, st) != hipSuccess))
     return drain(NGHTTP2_AMD_ERR_FATAL);
-  const int rv = nghttp2_amd_hd_huff_decode_batch_auto(src, src_off, nh, hb, dst, out_bytes, d_slot, d_st,
-                                                       nullptr, nullptr, stream);
+  int rv = nghttp2_amd_hd_huff_decode_batch_auto(src, src_off, nh, hb, dst, out_bytes, d_slot, d_st, nullptr, nullptr,
+                                                 stream);
+  if (!rv && want.checks)
+    rv = nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, ml.at<uint8_t>(d_meta, ml.masks), stream);
+  if (!rv && want.tokens)
+    rv = nghttp2_amd_hd_name_tokens_len_batch(dst, d_slot, d_st, nh, ml.at<int32_t>(d_meta, ml.tokens), nullptr, stream);
+  if (!rv && want.http)
+    rv = nghttp2_amd_hd_http_facts_batch(dst, d_slot, d_st, nh, ml.at<uint32_t>(d_meta, ml.facts),
+                                         ml.at<int64_t>(d_meta, ml.numbers), stream);
   if (rv) return drain(rv);
-  if (checks) {
-    const int rc =
-        nghttp2_amd_hd_check_fields_batch(dst, d_slot, d_st, nh, (uint8_t *)(d_st + nh) + http_bytes + tok_bytes, stream);
-    if (rc) return drain(rc);
-  }
-  if (tokens) {
-    const int rc = nghttp2_amd_hd_name_tokens_len_batch(dst, d_slot, d_st, nh,
-                                                        (int32_t *)((uint8_t *)(d_st + nh) + http_bytes), nullptr, stream);
-    if (rc) return drain(rc);
-  }
-  if (http) {
-    int64_t *d_num = (int64_t *)((uint8_t *)(d_st + nh) + http_pad);
-    const int rc = nghttp2_amd_hd_http_facts_batch(dst, d_slot, d_st, nh, (uint32_t *)(d_num + nh), d_num, stream);
-    if (rc) return drain(rc);
-  }
-  uint32_t *h_slot = h_meta + slots;
-  int32_t *h_st = (int32_t *)(h_slot + slots);
   if (!zero_copy &&
       (hipMemcpyAsync(E.h_out.p, dst, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipMemcpyAsync(h_slot, d_slot, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipMemcpyAsync(h_st, d_st, nh * sizeof(int32_t) + http_bytes + tok_bytes + chk_bytes, hipMemcpyDeviceToHost,
-                      st) != hipSuccess))
+       hipMemcpyAsync(ml.at<void>(h_meta, ml.slots), d_slot, ml.words, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(ml.at<void>(h_meta, ml.status), d_st, ml.end - ml.status, hipMemcpyDeviceToHost, st) !=
+           hipSuccess))
     return drain(NGHTTP2_AMD_ERR_FATAL);
-  const uint8_t *h_tail = (const uint8_t *)(h_st + nh);  // what follows the status words
-  const int64_t *h_num = (const int64_t *)(h_tail + http_pad);
   *ls = LitSrc{E.h_out.as<uint8_t>(),
-               h_slot,
-               h_st,
-               checks ? h_tail + http_bytes + tok_bytes : nullptr,
-               tokens ? (const int32_t *)(h_tail + http_bytes) : nullptr,
-               http ? (const uint32_t *)(h_num + nh) : nullptr,
-               http ? h_num : nullptr};
+               ml.at<uint32_t>(h_meta, ml.slots),
+               ml.at<int32_t>(h_meta, ml.status),
+               want.checks ? ml.at<uint8_t>(h_meta, ml.masks) : nullptr,
+               want.tokens ? ml.at<int32_t>(h_meta, ml.tokens) : nullptr,
+               want.http ? ml.at<uint32_t>(h_meta, ml.facts) : nullptr,
+               want.http ? ml.at<int64_t>(h_meta, ml.numbers) : nullptr};
   return 0;
 }
 
@@ -974,26 +937,10 @@ bool may_cut(const Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
   return false;
 }
 
-// One replayed block's fields into the caller's field array at nv_base and arena at ar_base.
-void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_base, nghttp2_amd_hd_nv *nva,
-                 uint8_t *arena, uint8_t *checks, int32_t *tokens, int32_t *verdicts) {
-  const uint32_t ab = (uint32_t)ar_base;
-  if (!o.bytes.empty()) memcpy(arena + ab, o.bytes.data(), o.bytes.size());
-  nghttp2_amd_hd_nv *d = nva + nv_base;
-  for (const Rec &r : o.recs)
-    *d++ = nghttp2_amd_hd_nv{block, ab + r.name_off, r.name_len, ab + r.value_off, r.value_len, r.flags};
-  if (checks) {
-    uint8_t *c = checks + 2 * nv_base;
-    for (const Rec &r : o.recs) *c++ = r.cn, *c++ = r.cv;
-  }
-  if (tokens) {
-    int32_t *t = tokens + nv_base;
-    for (const Rec &r : o.recs) *t++ = r.tk;
-  }
-  if (verdicts) {
-    int32_t *t = verdicts + nv_base;
-    for (const Rec &r : o.recs) *t++ = r.vd;
-  }
+// One replayed block's fields into the caller's arrays: field nv_base on, bytes at ar_base.
+void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_base, const FieldOut &fo) {
+  if (!o.bytes.empty()) memcpy(fo.arena + ar_base, o.bytes.data(), o.bytes.size());
+  for (const Rec &r : o.recs) fo.put(nv_base++, block, (uint32_t)ar_base, r);
 }
 
 // "replay direct" -- pass 2 for a batch of one connection (a serial replay
@@ -1002,12 +949,12 @@ void place_block(const BlockOut &o, uint32_t block, size_t nv_base, size_t ar_ba
 // of one connection).  A block whose own output bound may pass the caps is
 // replayed into a scratch buffer from a copy of the table, and placed if it
 // fits, else the table is restored and the batch cut there.
-int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, void *stream, Phases &ph) {
+int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, Want want, const Dest &d, void *stream, Phases &ph) {
   if (ls.st && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NGHTTP2_AMD_ERR_FATAL;
   ph.mark("gpu wait");
   nghttp2_amd_hd_inflater *c = E.conns[0];
-  DirectSink ds{d.arena, d.nva, d.block_status, d.nv_checks, d.nv_tokens, d.nv_verdicts};
-  const bool htp = d.http(), chk = d.nv_checks != nullptr || htp, tok = d.nv_tokens != nullptr || htp;
+  DirectSink ds{d.fo, d.block_status};
+  const bool htp = want.http;
   uint32_t cut = nblocks;
   for (uint32_t i = 0; i < nblocks; ++i) {
     const Block &b = E.bl[i];
@@ -1017,20 +964,20 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
     ds.block = i;
     HttpRun hr = htp ? d.run(i) : HttpRun{};
     if (ds.nv + b.nv <= d.nva_cap && ar_b <= d.arena_cap - ds.ar) {
-      replay_block(c, b, ls, chk, tok, htp ? &hr : nullptr, ds);
+      replay_block(c, b, ls, want, htp ? &hr : nullptr, ds);
       if (htp) d.set_http(i, hr.st, hr.result);
       continue;
     }
     nghttp2_amd_hd_inflater keep = *c;
     BlockOut scratch;
     BlockSink bs{scratch};
-    replay_block(c, b, ls, chk, tok, htp ? &hr : nullptr, bs);
+    replay_block(c, b, ls, want, htp ? &hr : nullptr, bs);
     if (ds.nv + scratch.recs.size() > d.nva_cap || scratch.bytes.size() > d.arena_cap - ds.ar) {
       *c = std::move(keep);
       cut = i;
       break;
     }
-    place_block(scratch, i, ds.nv, ds.ar, d.nva, d.arena, d.nv_checks, d.nv_tokens, d.nv_verdicts);
+    place_block(scratch, i, ds.nv, ds.ar, d.fo);
     if (htp) d.set_http(i, hr.st, hr.result);
     ds.nv += scratch.recs.size();
     ds.ar += scratch.bytes.size();
@@ -1052,7 +999,7 @@ int replay_direct(Engine &E, uint32_t nblocks, const LitSrc &ls, const Dest &d, 
 // the caller's buffers is cut at the first block that does not fit, and the tables
 // replayed up to there from snapshots (a copy of every table, if cut_possible).
 int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_t nblocks, const LitSrc &ls,
-                   const Dest &d, bool cut_possible, void *stream, Phases &ph) {
+                   Want want, const Dest &d, bool cut_possible, void *stream, Phases &ph) {
   const std::vector<nghttp2_amd_hd_inflater *> &conns = E.conns;
   std::vector<nghttp2_amd_hd_inflater> snap;
   if (cut_possible) {
@@ -1065,14 +1012,14 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
   // replay allocates only while they grow
   std::vector<BlockOut> &outs = E.outs;
   if (outs.size() < nblocks) outs.resize(nblocks);
-  const bool htp = d.http(), chk = d.nv_checks != nullptr || htp, tok = d.nv_tokens != nullptr || htp;
+  const bool htp = want.http;
   parallel_for(conns.size(), 1, [&](size_t c) {
     for (uint32_t j = E.cstart[c]; j < E.cstart[c + 1]; ++j) {
       const uint32_t i = E.corder[j];
       BlockSink bs{outs[i]};
       // (the caller's state is read here and written when the block is placed)
       HttpRun hr = htp ? d.run(i) : HttpRun{};
-      replay_block(conns[c], E.bl[i], ls, chk, tok, htp ? &hr : nullptr, bs);
+      replay_block(conns[c], E.bl[i], ls, want, htp ? &hr : nullptr, bs);
       if (htp) outs[i].hst = hr.st, outs[i].hres = hr.result;
     }
   });
@@ -1106,7 +1053,7 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
     // the caller's again)
     for (uint32_t i = 0; i < cut; ++i) {
       HttpRun hr = htp ? d.run(i) : HttpRun{};
-      replay_block(inflaters[i], E.bl[i], ls, chk, tok, htp ? &hr : nullptr, ss);
+      replay_block(inflaters[i], E.bl[i], ls, want, htp ? &hr : nullptr, ss);
     }
     for (uint32_t j = cut; j < nblocks; ++j) {
       d.block_status[j] = NGHTTP2_AMD_ERR_BUFFER_ERROR;
@@ -1114,8 +1061,7 @@ int replay_grouped(Engine &E, nghttp2_amd_hd_inflater *const *inflaters, uint32_
     }
   }
   parallel_for(cut, 256, [&](size_t i) {
-    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.nva, d.arena, d.nv_checks, d.nv_tokens,
-                d.nv_verdicts);
+    place_block(outs[i], (uint32_t)i, nv_base[i], ar_base[i], d.fo);
     d.block_status[i] = outs[i].status;
     if (htp) d.set_http((uint32_t)i, outs[i].hst, outs[i].hres);
   });
@@ -1272,14 +1218,13 @@ int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflater *const *inflaters
   Phases ph("inflate");
   std::lock_guard<std::mutex> guard(engine().mu);
   Engine &E = engine();
-  const Dest dest{nva, nva_cap, nva_used, arena, arena_cap, arena_used, block_status, nv_checks, nv_tokens,
-                  block_modes, block_state, nv_verdicts, block_http};
+  const Want want(nv_checks != nullptr, nv_tokens != nullptr, http);
+  const Dest dest{{nva, arena, nv_checks, nv_tokens, nv_verdicts}, nva_cap, nva_used, arena_cap, arena_used,
+                  block_status, block_modes, block_state, block_http};
   parse_blocks(E, nblocks, blocks, block_lens);
   ph.mark("parse blocks");
   LitSrc ls;
-  if (const int rv = stage_decode(E, nblocks, nv_checks != nullptr || http, nv_tokens != nullptr || http, http, stream,
-                                   ph, &ls))
-    return rv;
+  if (const int rv = stage_decode(E, nblocks, want, stream, ph, &ls)) return rv;
   ph.mark("gpu issued");
   // (the decode runs while the host groups the blocks by connection and
   // bounds the output; replay waits for it)
@@ -1287,8 +1232,8 @@ int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflater *const *inflaters
   ph.mark("group");
   const bool cut_possible = may_cut(E, inflaters, nblocks, dest);
   ph.mark("bound");
-  if (E.conns.size() == 1) return replay_direct(E, nblocks, ls, dest, stream, ph);
-  return replay_grouped(E, inflaters, nblocks, ls, dest, cut_possible, stream, ph);
+  if (E.conns.size() == 1) return replay_direct(E, nblocks, ls, want, dest, stream, ph);
+  return replay_grouped(E, inflaters, nblocks, ls, want, dest, cut_possible, stream, ph);
 }
 
 }  // extern "C"

@@ -594,14 +594,14 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
     the field/arena buffers is cut at the first block that does not fit
     (status NGHTTP2_ERR_BUFFER_ERROR from there on, those blocks not
     applied); with retry the rest is resubmitted with buffers twice the size.
-    With checks the call is nghttp2_amd_hd_inflate_blocks_checked and a third
+    With checks the call is equivalent to nghttp2_amd_hd_inflate_blocks_checked and a third
     result follows: a uint8 array (nfields, 2) of the CHECK_* masks of every
     emitted field's name and value, in the order of the fields.
-    With tokens the call is nghttp2_amd_hd_inflate_blocks_fields and one more
+    With tokens the call is equivalent to nghttp2_amd_hd_inflate_blocks_fields and one more
     result follows (after the masks when both are asked for): an int32 array
     (nfields,) of lookup_token of every emitted field's name, as
     nghttp2_hd_inflate_hd_nv sets nv.token.
-    With http (one HTTP_MODE_* value per block) the call is
+    With http (one HTTP_MODE_* value per block) the call is equivalent to
     nghttp2_amd_hd_inflate_blocks_http and three more results follow: an int32
     array (nfields,) of nghttp2_http_on_header's verdict for every emitted
     field (HTTP_NOT_EXAMINED after a block's first stream error), a structured
@@ -611,10 +611,13 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
     NGHTTP2_ERR_HEADER_COMP).  http_state gives the states before the blocks,
     one (http_flags, status_code, content_length) per block; None is a fresh
     stream, (0, -1, -1), for every block.
+    Every call goes through nghttp2_amd_hd_inflate_blocks_http, with NULL for
+    the arrays not asked for (the other three entry points are that, in C).
     The blocks go in as one joined buffer and the fields come out of
     uninitialised numpy buffers (no per-block ctypes objects, no zero fill)."""
     L = _inflate_lib()
     nb = len(blocks)
+    modes_all = states_all = bhttp_all = None  # (without http, all four HTTP arguments are NULL)
     if http is not None:
         modes_all = np.fromiter((int(m) for m in http), dtype=np.uint8, count=nb)
         states_all = np.empty(nb, dtype=_HTTP_STATE_DTYPE)
@@ -649,7 +652,9 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
     fields = [[] for _ in range(nb)]
     masks, toks, verds = [], [], []
     first = 0
-    vp = ctypes.c_void_p
+
+    def ptr(a):  # an array's address, NULL for one not asked for
+        return None if a is None else ctypes.c_void_p(a.ctypes.data)
     while first < nb:
         m = nb - first
         ptrs = np.ascontiguousarray(ptrs_all[first:])
@@ -659,37 +664,15 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
         arena = np.empty(max(1, arena_cap), dtype=np.uint8)
         st = np.empty(m, dtype=np.int32)
         nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
-        if http is not None:
-            chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8) if checks else None
-            tk = np.empty(max(1, nva_cap), dtype=np.int32) if tokens else None
-            vd = np.empty(max(1, nva_cap), dtype=np.int32)
-            # (views of the callers' slices: the states are updated in place)
-            rv = L.nghttp2_amd_hd_inflate_blocks_http(
-                vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
-                vp(nva.ctypes.data), nva_cap, ctypes.byref(nv_used), vp(arena.ctypes.data),
-                arena_cap, ctypes.byref(ar_used), vp(st.ctypes.data),
-                vp(chk.ctypes.data) if checks else None, vp(tk.ctypes.data) if tokens else None,
-                vp(modes_all[first:].ctypes.data), vp(states_all[first:].ctypes.data),
-                vp(vd.ctypes.data), vp(bhttp_all[first:].ctypes.data), s)
-        elif tokens:
-            chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8) if checks else None
-            tk = np.empty(max(1, nva_cap), dtype=np.int32)
-            rv = L.nghttp2_amd_hd_inflate_blocks_fields(
-                vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
-                vp(nva.ctypes.data), nva_cap, ctypes.byref(nv_used), vp(arena.ctypes.data),
-                arena_cap, ctypes.byref(ar_used), vp(st.ctypes.data),
-                vp(chk.ctypes.data) if checks else None, vp(tk.ctypes.data), s)
-        elif checks:
-            chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8)
-            rv = L.nghttp2_amd_hd_inflate_blocks_checked(
-                vp(infs.ctypes.data), m, vp(ptrs.ctypes.data), vp(lens.ctypes.data),
-                vp(nva.ctypes.data), nva_cap, ctypes.byref(nv_used), vp(arena.ctypes.data),
-                arena_cap, ctypes.byref(ar_used), vp(st.ctypes.data), vp(chk.ctypes.data), s)
-        else:
-            rv = L.nghttp2_amd_hd_inflate_blocks(vp(infs.ctypes.data), m, vp(ptrs.ctypes.data),
-                                                 vp(lens.ctypes.data), vp(nva.ctypes.data), nva_cap,
-                                                 ctypes.byref(nv_used), vp(arena.ctypes.data), arena_cap,
-                                                 ctypes.byref(ar_used), vp(st.ctypes.data), s)
+        chk = np.empty((max(1, nva_cap), 2), dtype=np.uint8) if checks else None
+        tk = np.empty(max(1, nva_cap), dtype=np.int32) if tokens else None
+        vd = np.empty(max(1, nva_cap), dtype=np.int32) if http is not None else None
+        # (views of the callers' slices: the states are updated in place)
+        modes, states, bhttp = (a if a is None else a[first:] for a in (modes_all, states_all, bhttp_all))
+        rv = L.nghttp2_amd_hd_inflate_blocks_http(
+            ptr(infs), m, ptr(ptrs), ptr(lens), ptr(nva), nva_cap, ctypes.byref(nv_used), ptr(arena),
+            arena_cap, ctypes.byref(ar_used), ptr(st), ptr(chk), ptr(tk), ptr(modes), ptr(states),
+            ptr(vd), ptr(bhttp), s)
         if rv != NGHTTP2_ERR_BUFFER_ERROR:
             _check(rv, "inflate_blocks")
         raw = arena[:ar_used.value].tobytes()

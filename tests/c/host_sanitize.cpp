@@ -13,7 +13,9 @@
 //   2. randomized malformed blocks (random bytes, representation sequences
 //      with over-long and overflowing integers, table size updates, mutated
 //      valid blocks) over several inflaters and small output caps, checking
-//      every status and record against the buffers;
+//      every status and record against the buffers; each batch again through
+//      _checked, _fields or _http with all their arrays on a twin set of
+//      inflaters, whose fields and statuses must equal the plain call's;
 //   3. static-table-only deflates, inflated back;
 //   4. the JSON reader on mutated documents.
 //
@@ -82,10 +84,15 @@ struct Batch {
   std::vector<int32_t> status;
   size_t nv_used = 0, ar_used = 0;
   int rv = 0;
+  // the annotated calls' arrays (exactly the caps long: a write past one is a report)
+  std::vector<uint8_t> checks, modes;
+  std::vector<int32_t> tokens, verdicts, block_http;
+  std::vector<nghttp2_amd_hd_http_state> states;
 };
 
+// level 0: the plain call; 1: _checked; 2: _fields; 3: _http (block i in mode modes[i], from a fresh state)
 Batch inflate(const std::vector<nghttp2_amd_hd_inflater *> &inf, const std::vector<std::vector<uint8_t>> &blocks,
-              size_t nva_cap, size_t arena_cap) {
+              size_t nva_cap, size_t arena_cap, int level = 0, const std::vector<uint8_t> &modes = {}) {
   Batch b;
   const uint32_t n = (uint32_t)blocks.size();
   std::vector<const uint8_t *> ptrs(n);
@@ -97,9 +104,29 @@ Batch inflate(const std::vector<nghttp2_amd_hd_inflater *> &inf, const std::vect
   b.nva.resize(nva_cap ? nva_cap : 1);
   b.arena.resize(arena_cap ? arena_cap : 1);
   b.status.assign(n ? n : 1, 12345);
-  b.rv = nghttp2_amd_hd_inflate_blocks(inf.data(), n, ptrs.data(), lens.data(), b.nva.data(), nva_cap,
-                                       &b.nv_used, b.arena.data(), arena_cap, &b.ar_used, b.status.data(),
-                                       nullptr);
+  b.checks.assign(2 * nva_cap + 1, 0xEE);
+  b.tokens.assign(nva_cap + 1, 12345);
+  b.verdicts.assign(nva_cap + 1, 12345);
+  b.block_http.assign(n + 1, 12345);
+  b.states.assign(n + 1, nghttp2_amd_hd_http_state{0, -1, -1});
+  b.modes = modes;
+  b.modes.resize(n + 1);
+  if (level == 0)
+    b.rv = nghttp2_amd_hd_inflate_blocks(inf.data(), n, ptrs.data(), lens.data(), b.nva.data(), nva_cap, &b.nv_used,
+                                         b.arena.data(), arena_cap, &b.ar_used, b.status.data(), nullptr);
+  else if (level == 1)
+    b.rv = nghttp2_amd_hd_inflate_blocks_checked(inf.data(), n, ptrs.data(), lens.data(), b.nva.data(), nva_cap,
+                                                 &b.nv_used, b.arena.data(), arena_cap, &b.ar_used, b.status.data(),
+                                                 b.checks.data(), nullptr);
+  else if (level == 2)
+    b.rv = nghttp2_amd_hd_inflate_blocks_fields(inf.data(), n, ptrs.data(), lens.data(), b.nva.data(), nva_cap,
+                                                &b.nv_used, b.arena.data(), arena_cap, &b.ar_used, b.status.data(),
+                                                b.checks.data(), b.tokens.data(), nullptr);
+  else
+    b.rv = nghttp2_amd_hd_inflate_blocks_http(inf.data(), n, ptrs.data(), lens.data(), b.nva.data(), nva_cap,
+                                              &b.nv_used, b.arena.data(), arena_cap, &b.ar_used, b.status.data(),
+                                              b.checks.data(), b.tokens.data(), b.modes.data(), b.states.data(),
+                                              b.verdicts.data(), b.block_http.data(), nullptr);
   return b;
 }
 
@@ -203,23 +230,30 @@ void fuzz_inflate(const std::vector<std::vector<uint8_t>> &seeds, uint32_t iters
   uint64_t blocks = 0, ok = 0, comp = 0, buf = 0, fatal = 0;
   for (uint32_t it = 0; it < iters; ++it) {
     const uint32_t ninf = 1 + r.below(3);
-    std::vector<nghttp2_amd_hd_inflater *> pool(ninf);
-    for (auto &p : pool) {
-      CHECK(nghttp2_amd_hd_inflate_new(&p) == 0, "inflate_new");
+    // (twin: the same connections for the annotated calls)
+    std::vector<nghttp2_amd_hd_inflater *> pool(ninf), twin(ninf);
+    for (uint32_t c = 0; c < ninf; ++c) {
+      CHECK(nghttp2_amd_hd_inflate_new(&pool[c]) == 0 && nghttp2_amd_hd_inflate_new(&twin[c]) == 0, "inflate_new");
       const uint32_t t = r.below(6);
-      if (t == 0) nghttp2_amd_hd_inflate_change_table_size(p, 0);
-      else if (t == 1) nghttp2_amd_hd_inflate_change_table_size(p, (size_t)-1);  // (saturating bounds)
-      else if (t == 2) nghttp2_amd_hd_inflate_change_table_size(p, r.below(8192));
+      const size_t size = t == 0 ? 0 : t == 1 ? (size_t)-1 /* (saturating bounds) */ : r.below(8192);
+      if (t <= 2) {
+        nghttp2_amd_hd_inflate_change_table_size(pool[c], size);
+        nghttp2_amd_hd_inflate_change_table_size(twin[c], size);
+      }
     }
     // several batches on the same inflaters: the sticky bad state and the
     // table evolution carry over
     for (uint32_t rep = 0; rep < 3; ++rep) {
       const uint32_t nb = r.below(9);
       std::vector<std::vector<uint8_t>> bl(nb);
-      std::vector<nghttp2_amd_hd_inflater *> inf(nb);
+      std::vector<nghttp2_amd_hd_inflater *> inf(nb), tinf(nb);
+      std::vector<uint8_t> modes(nb);
       for (uint32_t i = 0; i < nb; ++i) {
         bl[i] = random_block(r, seeds);
-        inf[i] = pool[r.below(ninf)];
+        const uint32_t c = r.below(ninf);
+        inf[i] = pool[c];
+        tinf[i] = twin[c];
+        modes[i] = (uint8_t)r.below(32);  // any of the NGHTTP2_AMD_HTTP_MODE_* bits
       }
       const size_t nva_cap = r.below(4) == 0 ? r.below(6) : 256;
       const size_t arena_cap = r.below(4) == 0 ? r.below(200) : 1u << 16;
@@ -247,6 +281,33 @@ void fuzz_inflate(const std::vector<std::vector<uint8_t>> &seeds, uint32_t iters
         buf += s == NGHTTP2_AMD_ERR_BUFFER_ERROR;
         fatal += s == NGHTTP2_AMD_ERR_FATAL;
       }
+      // the same batch at an annotated level on the twins: the annotated
+      // replay, the cut, the restore and re-apply, each entry's lazy fill from
+      // whatever level inserted it
+      const int level = 1 + (int)r.below(3);
+      Batch a = inflate(tinf, bl, nva_cap, arena_cap, level, modes);
+      CHECK(a.rv == b.rv && a.nv_used == b.nv_used && a.ar_used == b.ar_used, "level %d: rv %d/%d, used %zu/%zu %zu/%zu",
+            level, a.rv, b.rv, a.nv_used, b.nv_used, a.ar_used, b.ar_used);
+      CHECK(a.status == b.status, "level %d: statuses differ", level);
+      CHECK(!memcmp(a.arena.data(), b.arena.data(), b.ar_used < a.ar_used ? b.ar_used : a.ar_used), "level %d: arena", level);
+      for (size_t k = 0; k < a.nv_used && k < b.nv_used; ++k) {
+        const nghttp2_amd_hd_nv &x = a.nva[k], &y = b.nva[k];
+        CHECK(x.block == y.block && x.name_off == y.name_off && x.name_len == y.name_len && x.value_off == y.value_off &&
+                  x.value_len == y.value_len && x.flags == y.flags,
+              "level %d: record %zu differs", level, k);
+        CHECK(a.checks[2 * k] < NGHTTP2_AMD_CHECK_INVALID && a.checks[2 * k + 1] < NGHTTP2_AMD_CHECK_INVALID,
+              "level %d: field %zu unchecked", level, k);
+        CHECK(level < 2 || (a.tokens[k] >= -1 && a.tokens[k] <= 67), "token %d", a.tokens[k]);
+        CHECK(level < 3 || a.verdicts[k] != 12345, "field %zu has no verdict", k);
+      }
+      // nothing is written past the fields in use, or past the blocks
+      CHECK(a.checks[2 * a.nv_used] == 0xEE && a.tokens[a.nv_used] == 12345 && a.verdicts[a.nv_used] == 12345 &&
+                a.block_http[nb] == 12345,
+            "level %d: an array written past its end", level);
+      for (uint32_t c = 0; c < ninf; ++c)
+        CHECK(nghttp2_amd_hd_inflate_get_dynamic_table_size(pool[c]) == nghttp2_amd_hd_inflate_get_dynamic_table_size(twin[c]) &&
+                  nghttp2_amd_hd_inflate_get_num_table_entries(pool[c]) == nghttp2_amd_hd_inflate_get_num_table_entries(twin[c]),
+              "level %d: the twin's table differs", level);
       for (auto *p : pool) {  // the table accessors on whatever state remains
         const size_t ne = nghttp2_amd_hd_inflate_get_num_table_entries(p);
         for (size_t idx = 1; idx <= ne; idx += 1 + r.below(7)) {
@@ -263,6 +324,7 @@ void fuzz_inflate(const std::vector<std::vector<uint8_t>> &seeds, uint32_t iters
       }
     }
     for (auto *p : pool) nghttp2_amd_hd_inflate_del(p);
+    for (auto *p : twin) nghttp2_amd_hd_inflate_del(p);
   }
   printf("fuzzed blocks: %llu (ok %llu, -523 %llu, -502 %llu, fatal %llu)\n", (unsigned long long)blocks,
          (unsigned long long)ok, (unsigned long long)comp, (unsigned long long)buf, (unsigned long long)fatal);

@@ -37,8 +37,9 @@
            the string lane's own reads; and on 4,096 numbers of 16 KiB of zeros.
   inflate_http  nghttp2_amd_hd_inflate_blocks_http against
            nghttp2_amd_hd_inflate_blocks_fields with both arrays on the
-           2,048-block batch, alternated; with NGHTTP2_AMD_OTHER_LIB, that
-           build's _fields against this build's in the same process.
+           and the plain nghttp2_amd_hd_inflate_blocks on the 2,048-block
+           batch, alternated; with NGHTTP2_AMD_OTHER_LIB, that build's three
+           calls against this build's in the same process.
 
 With NGHTTP2_AMD_OTHER_LIB the names, check, names_len and http_facts rows
 also make the same call from that build, alternated call by call with this
@@ -450,8 +451,8 @@ def bench_http_facts(steps=30):
 def bench_inflate_http(nconn=256, per_conn=8, fields=16, alternations=15):
     """The C call of the 2,048-block inflate row, alternated call by call (no
     indexing: every call sees the same tables): _fields with both arrays and
-    _http with all its arrays; with NGHTTP2_AMD_OTHER_LIB, that build's
-    _fields too.  Every block is run as a request on a fresh state, so every
+    _http with all its arrays, and the plain call; with NGHTTP2_AMD_OTHER_LIB,
+    that build's three too.  Every block is run as a request on a fresh state, so every
     one of its fields is stepped (asserted: no field is left unexamined) and
     the request's block end runs."""
     import ctypes
@@ -492,30 +493,38 @@ def bench_inflate_http(nconn=256, per_conn=8, fields=16, alternations=15):
             return dt
         return g
 
-    def http_call():
-        for i in range(m):
-            states[i].http_flags, states[i].status_code, states[i].content_length = 0, -1, -1
-        return timed(lambda: L.nghttp2_amd_hd_inflate_blocks_http(
-            ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
-            chk, tk, modes, states, vd, bh, s))()
-    calls = {"fields": timed(lambda: L.nghttp2_amd_hd_inflate_blocks_fields(
-        ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
-        chk, tk, s)), "http": http_call}
+    def http_call(lib, ip):
+        def f():
+            for i in range(m):
+                states[i].http_flags, states[i].status_code, states[i].content_length = 0, -1, -1
+            return timed(lambda: lib.nghttp2_amd_hd_inflate_blocks_http(
+                ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
+                chk, tk, modes, states, vd, bh, s))()
+        return f
+
+    def three(lib, ip, prefix):  # the _fields, _http and plain calls of one build on its own inflaters
+        return {prefix + "fields": timed(lambda: lib.nghttp2_amd_hd_inflate_blocks_fields(
+                    ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used),
+                    stc, chk, tk, s)),
+                prefix + "http": http_call(lib, ip),
+                prefix + "plain": timed(lambda: lib.nghttp2_amd_hd_inflate_blocks(
+                    ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used),
+                    stc, s))}
+    calls = three(L, ip, "")
     other = os.environ.get("NGHTTP2_AMD_OTHER_LIB")
     if other:
         P = ctypes.CDLL(other)
         vp = ctypes.c_void_p
         P.nghttp2_amd_hd_inflate_new.argtypes = [ctypes.POINTER(vp)]
-        P.nghttp2_amd_hd_inflate_blocks_fields.argtypes = L.nghttp2_amd_hd_inflate_blocks_fields.argtypes
+        for fn in ("nghttp2_amd_hd_inflate_blocks", "nghttp2_amd_hd_inflate_blocks_fields",
+                   "nghttp2_amd_hd_inflate_blocks_http"):
+            getattr(P, fn).argtypes = getattr(L, fn).argtypes
         pin = []
         for _ in range(nconn):
             q = vp()
             assert P.nghttp2_amd_hd_inflate_new(ctypes.byref(q)) == 0
             pin.append(q.value)
-        pip = (ctypes.c_void_p * m)(*[pin[c] for c in conns])
-        calls["other_fields"] = timed(lambda: P.nghttp2_amd_hd_inflate_blocks_fields(
-            pip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena, arena_cap, ctypes.byref(ar_used), stc,
-            chk, tk, s))
+        calls.update(three(P, (ctypes.c_void_p * m)(*[pin[c] for c in conns]), "other_"))
     for _ in range(3):
         for c in calls.values():
             c()
@@ -524,7 +533,7 @@ def bench_inflate_http(nconn=256, per_conn=8, fields=16, alternations=15):
         for k, c in calls.items():
             ts[k].append(c())
     # what the last _http call left: every field stepped, every block ended
-    http_call()
+    calls["http"]()
     verdicts = np.frombuffer(vd, dtype=np.int32)[:nv_used.value]
     results = np.frombuffer(bh, dtype=np.int32)[:m]
     assert not np.any(verdicts == hd.HTTP_NOT_EXAMINED) and not np.any(verdicts == hd.NGHTTP2_ERR_HTTP_HEADER)
@@ -542,10 +551,10 @@ def bench_inflate_http(nconn=256, per_conn=8, fields=16, alternations=15):
     out["http_minus_fields_us_median"] = round((out["http_s_median"] - out["fields_s_median"]) * 1e6, 1)
     out["http_minus_fields_us_best"] = round((out["http_s_best"] - out["fields_s_best"]) * 1e6, 1)
     if other:
-        out["fields_minus_other_fields_us_median"] = round(
-            (out["fields_s_median"] - out["other_fields_s_median"]) * 1e6, 1)
-        out["fields_minus_other_fields_us_best"] = round(
-            (out["fields_s_best"] - out["other_fields_s_best"]) * 1e6, 1)
+        for k in ("fields", "http", "plain"):
+            for stat in ("median", "best"):
+                out["%s_minus_other_%s_us_%s" % (k, k, stat)] = round(
+                    (out["%s_s_%s" % (k, stat)] - out["other_%s_s_%s" % (k, stat)]) * 1e6, 1)
     return out
 
 
