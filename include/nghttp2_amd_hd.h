@@ -503,6 +503,187 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_http_on_request_headers(nghttp2_amd_hd_htt
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_http_on_response_headers(nghttp2_amd_hd_http_state *state);
 
 /* ------------------------------------------------------------------ */
+/* Header blocks into representations and Huffman literals             */
+/* ------------------------------------------------------------------ */
+/*
+ * The representation layer of nghttp2_hd_inflate_hd_nv
+ * (lib/nghttp2_hd.c:1942-1985 opcode dispatch, decode_length :882-945) for
+ * complete header blocks: a block is cut into its representations -- table
+ * size updates, indexed fields, literal fields with their string literals'
+ * extents -- which needs no table state, so every block of a batch is parsed
+ * on its own.  What the representations mean (index resolution, insertion
+ * with eviction, the size update rules) is the replay's, not this layer's.
+ *
+ * One representation.  Offsets are positions in the wire the block was
+ * parsed from (the wire pool of a batch; the block itself for
+ * nghttp2_amd_hd_parse_block), lengths are the encoded lengths on the wire.
+ *   kind       NGHTTP2_AMD_HD_OP_SIZE / _INDEXED / _LITERAL
+ *   flags      of a LITERAL: INDEX_REQUIRED (opcode 01xxxxxx: the field enters
+ *              the dynamic table), NO_INDEX (0001xxxx: NGHTTP2_NV_FLAG_NO_INDEX),
+ *              NEW_NAME (the name is a string literal; clear: `value` is its
+ *              index), NAME_HUFF / VALUE_HUFF (the literal's H bit)
+ *   value      SIZE: the new maximum; INDEXED and a LITERAL without NEW_NAME:
+ *              the index (1-based as on the wire; 0 is the replay's error)
+ *   name_off, name_len    the name literal's bytes (NEW_NAME), else 0
+ *   value_off, value_len  the value literal's bytes (LITERAL), else 0
+ *   name_lit, value_lit   the literal's number among the Huffman literals
+ *              (batch: of the whole batch; one block: of the block), or -1
+ *              for a raw literal or none
+ * Huffman literals are numbered in wire order: blocks in batch order,
+ * representations in order within a block, a name before its value.  A block
+ * that fails keeps the representations completed before the failure, and
+ * their literals keep their numbers, because the reference has emitted
+ * those fields by then (the replay emits them too).  A Huffman literal of
+ * length 0 is a Huffman literal.
+ */
+typedef struct {
+  uint8_t kind;
+  uint8_t flags;
+  uint16_t reserved; /* 0 */
+  uint32_t value;
+  uint32_t name_off, name_len;
+  uint32_t value_off, value_len;
+  int32_t name_lit, value_lit;
+} nghttp2_amd_hd_op; /* 32 bytes */
+
+#define NGHTTP2_AMD_HD_OP_SIZE 0u
+#define NGHTTP2_AMD_HD_OP_INDEXED 1u
+#define NGHTTP2_AMD_HD_OP_LITERAL 2u
+
+#define NGHTTP2_AMD_HD_OP_INDEX_REQUIRED 0x01u
+#define NGHTTP2_AMD_HD_OP_NO_INDEX 0x02u
+#define NGHTTP2_AMD_HD_OP_NEW_NAME 0x04u
+#define NGHTTP2_AMD_HD_OP_NAME_HUFF 0x08u
+#define NGHTTP2_AMD_HD_OP_VALUE_HUFF 0x10u
+
+/*
+ * One block on the host (no GPU): the representations of in[0, len) go to
+ * ops[0, min(*nops, ops_cap)) and their number to *nops.  The rules are
+ * exactly the inflater's: prefix integers as nghttp2_amd_hd_decode_length
+ * (a group at a shift of 32 or more, a carry past UINT32_MAX, or an integer
+ * the block end cuts off fails), string literals of at most 65536
+ * (NGHTTP2_HD_MAX_NV) bytes that the rest of the block covers.  Returns
+ *   0                             the whole block is representations;
+ *   NGHTTP2_AMD_ERR_HEADER_COMP   the bytes after the last completed
+ *                                 representation are none; the completed
+ *                                 ones are written and counted;
+ *   NGHTTP2_AMD_ERR_BUFFER_ERROR  *nops > ops_cap: *nops is the count
+ *                                 needed, nothing at or past ops + ops_cap
+ *                                 was written (this comes before
+ *                                 HEADER_COMP: call again with room);
+ *   NGHTTP2_AMD_ERR_INVALID_ARGUMENT  nops is NULL, in is NULL with len > 0,
+ *                                 ops is NULL with ops_cap > 0, or len >
+ *                                 UINT32_MAX (the record's offsets are
+ *                                 uint32).
+ * The same code walks a block on the GPU (csrc/hd_parse.h).
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_parse_block(const uint8_t *in, size_t len, nghttp2_amd_hd_op *ops,
+                                                  size_t ops_cap, size_t *nops);
+
+/* totals[3] of a parse: 0, or why the batch's results are not complete */
+#define NGHTTP2_AMD_HD_PARSE_OVERFLOW_OPS 0x1u  /* more representations than ops_cap */
+#define NGHTTP2_AMD_HD_PARSE_OVERFLOW_U32 0x2u  /* a total does not fit the uint32 offsets */
+#define NGHTTP2_AMD_HD_PARSE_OVERFLOW_LITS 0x4u /* (gather) more Huffman literals than lits_cap */
+#define NGHTTP2_AMD_HD_PARSE_OVERFLOW_POOL 0x8u /* (gather) more Huffman bytes than pool_cap */
+
+/*
+ * Capacities that cannot overflow for `nblocks` blocks lying side by side
+ * (non-decreasing offsets) in `wire_bytes` bytes of wire: a representation
+ * takes at least one wire byte and so does a string literal, so
+ * *ops_cap = *lits_cap = max(wire_bytes, 1) entries, and the Huffman bytes
+ * are wire bytes: *pool_cap = align_up(wire_bytes, 16) + 16 bytes, which is
+ * also what the decode needs readable behind its input.  *ws_bytes is the
+ * parse's device workspace.  Any pointer may be NULL.  Returns 0, or
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT when wire_bytes > UINT32_MAX.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_parse_blocks_bound(uint64_t wire_bytes, uint32_t nblocks, size_t *ops_cap,
+                                                         size_t *lits_cap, size_t *pool_cap, size_t *ws_bytes);
+
+/*
+ * The representations of a batch of blocks, on the GPU.  Block i is
+ * wire[block_off[i], block_off[i+1]).
+ *
+ *   wire, block_off[n+1] : IN (device)
+ *   op_off[n+1]       : OUT: block i's records are ops[op_off[i], op_off[i+1])
+ *   ops, ops_cap      : OUT: the records, room for ops_cap of them
+ *   block_status[n]   : OUT: the block's number of representations, or
+ *                       NGHTTP2_AMD_ERR_HEADER_COMP when the block fails
+ *                       (its completed representations are still in ops, and
+ *                       op_off counts them)
+ *   lit_base[n+1]     : OUT: the number of the block's first Huffman literal;
+ *                       lit_base[n] is the batch's count
+ *   totals[4]         : OUT: {representations, Huffman literals, Huffman
+ *                       bytes, NGHTTP2_AMD_HD_PARSE_OVERFLOW_* bits}
+ *   workspace         : device scratch, >= the bound's ws_bytes
+ *
+ * Every record equals nghttp2_amd_hd_parse_block's for the block, with the
+ * offsets positions in `wire` and the literal numbers the batch's.  A block
+ * with block_off[i] > block_off[i+1] is not read and gets HEADER_COMP with
+ * no representation, as a string of the scan kernels gets INVALID.  Bytes
+ * outside a block never influence its result, and no byte outside the
+ * blocks is read.
+ *
+ * Three launches: the count (one lane per block walks it: representations,
+ * Huffman literals, Huffman bytes), a one-workgroup scan of the three counts
+ * into op_off, lit_base and totals, and the write (the same walk, storing
+ * records).  Every record store is checked against ops_cap: when the batch
+ * holds more, totals[3] has OVERFLOW_OPS, nothing at or past ops + ops_cap
+ * is written, and the records below it are valid.  When a total passes
+ * UINT32_MAX (only blocks that overlap can do that), totals[3] has
+ * OVERFLOW_U32 and no record, offset or status is valid.  Size the arrays
+ * by nghttp2_amd_hd_parse_blocks_bound and neither happens.
+ *
+ * Device pointers, asynchronous on `stream`.  n == 0 returns 0 and touches
+ * nothing.  A NULL wire, block_off, op_off, ops (with ops_cap > 0),
+ * block_status, lit_base, totals or workspace, or a workspace smaller than
+ * the bound's, is NGHTTP2_AMD_ERR_INVALID_ARGUMENT.  A block's status is
+ * int32: a block of 2^31 representations or more is out of scope.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_parse_blocks_batch(const uint8_t *wire, const uint32_t *block_off,
+                                                         uint32_t nblocks, uint32_t *op_off,
+                                                         nghttp2_amd_hd_op *ops, size_t ops_cap,
+                                                         int32_t *block_status, uint32_t *lit_base,
+                                                         uint32_t *totals, void *workspace, size_t ws_bytes,
+                                                         void *stream);
+
+/*
+ * Every Huffman literal of a parsed batch, copied into one pool in the
+ * decode's input layout: literal k (its number in the records) is
+ * pool[lit_off[k], lit_off[k+1]), the literals back to back from 0, so
+ * (pool, lit_off, totals[1] strings) goes to
+ * nghttp2_amd_hd_huff_decode_batch_auto as it is.
+ *
+ *   wire, wire_bytes  : the wire the records point into, and its size (a
+ *                       record reaching past it is not copied)
+ *   ops, ops_cap      : the parse's records and their capacity
+ *   totals            : the parse's totals (device): the counts are read
+ *                       there, so the call follows the parse on the stream
+ *                       with no host synchronisation; the gather ORs its own
+ *                       OVERFLOW_* bits into totals[3]
+ *   lit_off, lits_cap : OUT: lits_cap + 1 entries; [0, totals[1]] written
+ *   pool, pool_cap    : OUT: the literals' bytes; 16-byte aligned.  The
+ *                       decode reads its input to align_up(end, 16) + 16:
+ *                       the bound's pool_cap covers that.
+ *
+ * Does nothing when totals[3] is not 0 on entry.  More literals than
+ * lits_cap sets OVERFLOW_LITS and writes nothing; more Huffman bytes than
+ * pool_cap sets OVERFLOW_POOL, lit_off is valid, and no pool byte is
+ * written.  Three launches: the literals' lengths (a lane per record), a
+ * one-workgroup scan into lit_off, and the copy: a wave takes 64 consecutive
+ * records and copies their Huffman literals one after the other, its 64
+ * lanes on consecutive bytes.
+ *
+ * Device pointers, asynchronous on `stream`.  A batch without Huffman
+ * literals writes lit_off[0] = 0 and nothing else.  A NULL wire, ops,
+ * totals, lit_off or pool is NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_gather_literals_batch(const uint8_t *wire, size_t wire_bytes,
+                                                            const nghttp2_amd_hd_op *ops, size_t ops_cap,
+                                                            uint32_t *totals, uint32_t *lit_off,
+                                                            size_t lits_cap, uint8_t *pool, size_t pool_cap,
+                                                            void *stream);
+
+/* ------------------------------------------------------------------ */
 /* Batched HPACK inflate front-end               */
 /* ------------------------------------------------------------------ */
 /*

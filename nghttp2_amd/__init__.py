@@ -29,6 +29,7 @@ from .hd import (  # noqa: F401
     check_field,
     decode_length,
     lib,
+    parse_block,
     lib_path,
     deflate_blocks,
     inflate_blocks,

@@ -89,6 +89,26 @@ _HTTP_STATE_DTYPE = np.dtype([("http_flags", "<u4"), ("status_code", "<i4"),
                               ("content_length", "<i8")])
 assert _HTTP_STATE_DTYPE.itemsize == ctypes.sizeof(HttpState)
 
+# parse_block / parse_blocks: one representation of a header block
+# (nghttp2_amd_hd_op, 32 bytes).  Offsets are positions in the wire the block
+# was parsed from, lengths the encoded lengths; name_lit / value_lit number the
+# Huffman literals (-1: a raw literal or none).
+OP_SIZE, OP_INDEXED, OP_LITERAL = 0, 1, 2
+OP_INDEX_REQUIRED = 0x01
+OP_NO_INDEX = 0x02
+OP_NEW_NAME = 0x04
+OP_NAME_HUFF = 0x08
+OP_VALUE_HUFF = 0x10
+OP_DTYPE = np.dtype([("kind", "u1"), ("flags", "u1"), ("reserved", "<u2"), ("value", "<u4"),
+                     ("name_off", "<u4"), ("name_len", "<u4"), ("value_off", "<u4"),
+                     ("value_len", "<u4"), ("name_lit", "<i4"), ("value_lit", "<i4")])
+assert OP_DTYPE.itemsize == 32
+# totals[3] of parse_blocks / gather_huffman_literals
+PARSE_OVERFLOW_OPS = 0x1
+PARSE_OVERFLOW_U32 = 0x2
+PARSE_OVERFLOW_LITS = 0x4
+PARSE_OVERFLOW_POOL = 0x8
+
 _lib = None
 
 
@@ -154,6 +174,10 @@ def lib():
             ctypes.c_uint8, u32, ctypes.c_int64]
         L.nghttp2_amd_hd_http_on_request_headers.argtypes = [ctypes.POINTER(HttpState), u32]
         L.nghttp2_amd_hd_http_on_response_headers.argtypes = [ctypes.POINTER(HttpState)]
+        L.nghttp2_amd_hd_parse_block.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz)]
+        L.nghttp2_amd_hd_parse_blocks_bound.argtypes = [u64, u32] + [ctypes.POINTER(sz)] * 4
+        L.nghttp2_amd_hd_parse_blocks_batch.argtypes = [vp, vp, u32, vp, vp, sz, vp, vp, vp, vp, sz, vp]
+        L.nghttp2_amd_hd_gather_literals_batch.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -203,6 +227,53 @@ def http_on_request_headers(state, mode):
 
 def http_on_response_headers(state):
     return lib().nghttp2_amd_hd_http_on_response_headers(ctypes.byref(state))
+
+
+def parse_block(block, ops_cap=None):
+    """The representations of one complete header block, on the host
+    (nghttp2_amd_hd_parse_block; no GPU): (rv, ops).  rv is 0,
+    NGHTTP2_ERR_HEADER_COMP (ops holds the representations completed before
+    the failure) or, with an ops_cap too small, NGHTTP2_ERR_BUFFER_ERROR (ops
+    is then the count needed).  ops is a numpy array of OP_DTYPE; offsets are
+    positions in `block`, Huffman literals are numbered from 0."""
+    block = bytes(block)
+    buf = np.frombuffer(block + b"\0", dtype=np.uint8)
+    cap = len(block) if ops_cap is None else int(ops_cap)
+    ops = np.zeros(max(1, cap), dtype=OP_DTYPE)
+    nops = ctypes.c_size_t()
+    rv = lib().nghttp2_amd_hd_parse_block(buf.ctypes.data, len(block), ops.ctypes.data, cap,
+                                          ctypes.byref(nops))
+    if rv == NGHTTP2_ERR_BUFFER_ERROR:
+        return rv, nops.value
+    if rv not in (0, NGHTTP2_ERR_HEADER_COMP):
+        _check(rv, "parse_block")
+    return rv, ops[:nops.value]
+
+
+def parse_blocks_bound(wire_bytes, nblocks):
+    """Capacities that cannot overflow for nblocks blocks side by side in
+    wire_bytes bytes: (ops_cap, lits_cap, pool_cap, ws_bytes)."""
+    out = [ctypes.c_size_t() for _ in range(4)]
+    _check(lib().nghttp2_amd_hd_parse_blocks_bound(int(wire_bytes), int(nblocks),
+                                                   *[ctypes.byref(o) for o in out]),
+           "parse_blocks_bound")
+    return tuple(o.value for o in out)
+
+
+# What HuffmanBatchCodec.parse_blocks returns: device tensors.  ops is int32
+# [ops_cap, 8], one 32-byte record per row (ops_to_numpy gives the structured
+# view); op_off / lit_base are int32[n+1] holding uint32; block_status is
+# int32[n]; totals is int32[4] = {representations, Huffman literals, Huffman
+# bytes, PARSE_OVERFLOW_* bits}.  wire_bytes is the wire's size on the host.
+ParsedBlocks = collections.namedtuple("ParsedBlocks", "ops op_off block_status lit_base totals wire_bytes")
+
+
+def ops_to_numpy(ops, count=None):
+    """A parse's records (ParsedBlocks.ops, or its first `count` rows) on the
+    host as a numpy array of OP_DTYPE (synchronises)."""
+    if count is not None:
+        ops = ops[:count]
+    return ops.contiguous().cpu().numpy().view(OP_DTYPE).reshape(-1)
 
 
 def tables_ref_layout():
@@ -370,6 +441,63 @@ class HuffmanBatchCodec:
             _p(pool), _p(off), _p(len), n, _p(facts), _p(number), _stream(stream))
         _check(rv, "http_facts_batch")
         return facts[:n], number[:n]
+
+    def parse_blocks(self, wire, block_off, wire_bytes=None, ops_cap=None, stream=None):
+        """The representations of every block of a batch
+        (nghttp2_amd_hd_parse_blocks_batch): block i is
+        wire[block_off[i]:block_off[i+1]] (uint8 pool, int32[n+1] holding
+        uint32).  Returns a ParsedBlocks of device tensors; nothing is read
+        back.  ops_cap defaults to the bound for wire_bytes (default
+        wire.numel()), which cannot overflow for blocks side by side; with a
+        smaller one, totals[3] reports PARSE_OVERFLOW_OPS."""
+        torch = self.torch
+        n = block_off.numel() - 1
+        if wire_bytes is None:
+            wire_bytes = wire.numel()
+        if wire.numel() == 0:  # an all-empty batch: a pointer the library accepts (never read)
+            wire = self._empty(16, torch.uint8, stream)
+        cap, _, _, need = parse_blocks_bound(wire_bytes, n)
+        if ops_cap is not None:
+            cap = int(ops_cap)
+        ops = self._empty((max(1, cap), 8), torch.int32, stream)
+        op_off = self._empty(n + 1, torch.int32, stream)
+        lit_base = self._empty(n + 1, torch.int32, stream)
+        status = self._empty(max(1, n), torch.int32, stream)
+        totals = self._empty(4, torch.int32, stream)
+        if n == 0:
+            with torch.cuda.stream(self._on(stream)):
+                op_off.zero_(), lit_base.zero_(), totals.zero_()
+        ws = self._scratch_for("pws", need, stream)
+        rv = self.L.nghttp2_amd_hd_parse_blocks_batch(
+            _p(wire), _p(block_off), n, _p(op_off), _p(ops), cap, _p(status), _p(lit_base),
+            _p(totals), _p(ws), ws.numel(), _stream(stream))
+        _check(rv, "parse_blocks_batch")
+        return ParsedBlocks(ops[:cap], op_off, status[:n], lit_base, totals, int(wire_bytes))
+
+    def gather_huffman_literals(self, wire, parsed, lits_cap=None, pool_cap=None, stream=None):
+        """Every Huffman literal of a parsed batch in one pool, in decode_auto's
+        input layout (nghttp2_amd_hd_gather_literals_batch): returns (pool
+        uint8, lit_off int32[lits_cap + 1]); literal k is
+        pool[lit_off[k]:lit_off[k+1]] for k < parsed.totals[1], and
+        decode_auto(pool, lit_off[:T + 1], enc_bytes=parsed.totals[2]) decodes
+        them.  The counts are read from parsed.totals on the device.  The caps
+        default to the bound; a pool_cap is the number of bytes that may be
+        written (the pool tensor keeps the decode's readable tail behind it)."""
+        torch = self.torch
+        if wire.numel() == 0:
+            wire = self._empty(16, torch.uint8, stream)
+        _, lcap, pcap, _ = parse_blocks_bound(parsed.wire_bytes, 0)
+        if lits_cap is not None:
+            lcap = int(lits_cap)
+        if pool_cap is not None:
+            pcap = int(pool_cap)
+        lit_off = self._empty(lcap + 1, torch.int32, stream)
+        pool = self._empty(((pcap + 15) // 16) * 16 + 16, torch.uint8, stream)
+        rv = self.L.nghttp2_amd_hd_gather_literals_batch(
+            _p(wire), parsed.wire_bytes, _p(parsed.ops), parsed.ops.shape[0], _p(parsed.totals),
+            _p(lit_off), lcap, _p(pool), pcap, _stream(stream))
+        _check(rv, "gather_literals_batch")
+        return pool, lit_off
 
     def emit_strings(self, src, src_off, raw_bytes=None, dst=None, dst_off=None, stream=None):
         """HPACK string literals (emit_string, lib/nghttp2_hd.c:1001-1044) for

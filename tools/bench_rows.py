@@ -41,6 +41,15 @@
            batch, alternated; with NGHTTP2_AMD_OTHER_LIB, that build's three
            calls against this build's in the same process.
 
+  parse    nghttp2_amd_hd_parse_blocks_batch + nghttp2_amd_hd_gather_literals_batch
+           on the 2,048-block batch: the six launches between two HIP events
+           on device-resident wire, and again with the wire's H2D copy in
+           front, alternated; beside them, in the same process, the host
+           phases they restate (`parse blocks`, `number+copy`) from
+           nghttp2_amd_hd_inflate_blocks' own trace (NGHTTP2_AMD_TRACE=1, which
+           the row sets: run it alone, or first).  Several runs; the spread
+           of the runs' medians is reported.
+
 With NGHTTP2_AMD_OTHER_LIB the names, check, names_len and http_facts rows
 also make the same call from that build, alternated call by call with this
 build's on the same resident pools (the `other_*` figures).
@@ -773,6 +782,151 @@ def bench_inflate_alt(nconn=256, per_conn=8, fields=16, alternations=7, index=Fa
             "per_alternation_cpu16_s": [round(x, 6) for x in cpu_med]}
 
 
+def bench_parse(nconn=256, per_conn=8, fields=16, runs=5, steps=20):
+    """Parse + gather of the 2,048-block batch on the GPU (the C calls on
+    tensors allocated once) against the inflater's host phases that do the
+    same work, in one process, alternating: each run times `steps` calls of
+    each GPU form between HIP events (and wall time around the calls and a
+    stream synchronisation, the figure a host caller would wait for), then
+    five traced nghttp2_amd_hd_inflate_blocks calls.  The row reports each
+    run's medians and the spread of those medians over the runs."""
+    import ctypes
+    import re
+    import statistics
+    import tempfile
+    os.environ["NGHTTP2_AMD_TRACE"] = "1"
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    blocks, conns = make_blocks(nconn, per_conn, fields)
+    m = len(blocks)
+    wire = b"".join(blocks)
+    W = len(wire)
+    off = np.cumsum([0] + [len(b) for b in blocks]).astype(np.uint32)
+    dev = torch.device("cuda:0")
+    codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    L = codec.L
+    pinned = torch.from_numpy(np.frombuffer(bytearray(wire), np.uint8)).pin_memory()
+    tw = pinned.to(dev)
+    tw2 = torch.empty_like(tw)
+    to = torch.from_numpy(off.view(np.int32)).to(dev)
+    ops_cap, lits_cap, pool_cap, ws_bytes = hd.parse_blocks_bound(W, m)
+    i32, u8 = torch.int32, torch.uint8
+    ops = torch.empty((ops_cap, 8), dtype=i32, device=dev)
+    op_off, lit_base = torch.empty(m + 1, dtype=i32, device=dev), torch.empty(m + 1, dtype=i32, device=dev)
+    status, totals = torch.empty(m, dtype=i32, device=dev), torch.empty(4, dtype=i32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=u8, device=dev)
+    lit_off = torch.empty(lits_cap + 1, dtype=i32, device=dev)
+    pool = torch.empty(pool_cap, dtype=u8, device=dev)
+    st = hd._stream(None)
+    p = hd._p
+
+    def parse(w):
+        rv = L.nghttp2_amd_hd_parse_blocks_batch(p(w), p(to), m, p(op_off), p(ops), ops_cap, p(status), p(lit_base),
+                                                 p(totals), p(ws), ws_bytes, st)
+        assert rv == 0
+
+    def gather(w):
+        rv = L.nghttp2_amd_hd_gather_literals_batch(p(w), W, p(ops), ops_cap, p(totals), p(lit_off), lits_cap,
+                                                    p(pool), pool_cap, st)
+        assert rv == 0
+
+    def both():
+        parse(tw)
+        gather(tw)
+
+    def with_h2d():
+        tw2.copy_(pinned, non_blocking=True)
+        parse(tw2)
+        gather(tw2)
+
+    calls = {"parse": lambda: parse(tw), "gather": lambda: gather(tw), "parse_gather": both,
+             "h2d_parse_gather": with_h2d}
+    # what the batch holds, checked against the host twin once
+    both()
+    torch.cuda.synchronize()
+    tot = [int(x) for x in totals.cpu().numpy().view(np.uint32)]
+    twin = [hd.parse_block(b)[1] for b in blocks]
+    assert tot[0] == sum(len(o) for o in twin) and tot[3] == 0
+    assert status.cpu().numpy().tolist() == [len(o) for o in twin]
+    huff = [(b, int(r[o]), int(r[n])) for b, t in zip(blocks, twin) for r in t
+            for f, o, n in ((hd.OP_NAME_HUFF, "name_off", "name_len"), (hd.OP_VALUE_HUFF, "value_off", "value_len"))
+            if r["flags"] & f]
+    assert tot[1] == len(huff) and tot[2] == sum(n for _, _, n in huff)
+    assert pool.cpu().numpy()[:tot[2]].tobytes() == b"".join(b[o:o + n] for b, o, n in huff)
+
+    # the inflater's C call, traced
+    LI = hd._inflate_lib()
+    keep = [ctypes.create_string_buffer(b, len(b)) for b in blocks]
+    ptrs = (ctypes.c_void_p * m)(*[ctypes.cast(k, ctypes.c_void_p) for k in keep])
+    lens = (ctypes.c_size_t * m)(*[len(b) for b in blocks])
+    nva_cap, arena_cap = W + 16, 8 * W + 4096
+    nva = (hd._Nv * nva_cap)()
+    arena = (ctypes.c_uint8 * arena_cap)()
+    stc = (ctypes.c_int32 * m)()
+    nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
+    infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+    ip = (ctypes.c_void_p * m)(*[infs[c].p.value for c in conns])
+
+    def inflate():
+        t0 = time.perf_counter()
+        rv = LI.nghttp2_amd_hd_inflate_blocks(ip, m, ptrs, lens, nva, nva_cap, ctypes.byref(nv_used), arena,
+                                              arena_cap, ctypes.byref(ar_used), stc, st)
+        assert rv == 0
+        return (time.perf_counter() - t0) * 1e6
+
+    def traced(n):
+        """n inflate calls with the library's stderr trace captured:
+        (call us, {phase: us}) per call."""
+        sys.stderr.flush()
+        with tempfile.TemporaryFile() as tmp:
+            saved = os.dup(2)
+            os.dup2(tmp.fileno(), 2)
+            try:
+                wall = [inflate() for _ in range(n)]
+            finally:
+                os.dup2(saved, 2)
+                os.close(saved)
+            tmp.seek(0)
+            text = tmp.read().decode("ascii", "replace")
+        ph = [dict((k.strip(), float(v)) for k, v in re.findall(r" ([a-z+ ]+?)=([0-9.]+)us", ln))
+              for ln in text.splitlines() if ln.startswith("[nghttp2_amd inflate]")]
+        return wall, ph
+
+    for _ in range(3):
+        inflate()
+    per_run = []
+    s = torch.cuda.current_stream()
+    for _ in range(runs):
+        r = alternate(calls, steps)
+        for k, c in calls.items():  # wall: the calls and a synchronisation
+            ts = []
+            for _ in range(steps):
+                s.synchronize()
+                t0 = time.perf_counter()
+                c()
+                s.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e6)
+            r[k + "_wall_us_median"] = round(statistics.median(ts), 1)
+        wall, ph = traced(5)
+        r["inflate_call_us_median"] = round(statistics.median(wall), 1)
+        for name in ("parse blocks", "number+copy"):
+            v = [x[name] for x in ph if name in x]
+            r["host_" + name.replace(" ", "_") + "_us_median"] = round(statistics.median(v), 1) if v else None
+        per_run.append(r)
+    keys = [k for k in per_run[0] if k.endswith("_median")]
+    spread = {}
+    for k in keys:
+        v = [r[k] for r in per_run if r[k] is not None]
+        if v:
+            spread[k] = {"median": round(statistics.median(v), 1), "min": min(v), "max": max(v)}
+    return {"blocks": m, "connections": nconn, "wire_bytes": W, "ops": tot[0], "huffman_literals": tot[1],
+            "huffman_bytes": tot[2], "runs": runs, "steps": steps, "over_runs": spread, "per_run": per_run,
+            "note": "GPU forms: HIP events around the C calls on preallocated tensors (_us_*), and wall time "
+                    "around the calls and a stream synchronisation (_wall_us_median); host phases: the "
+                    "inflater's own trace of the same batch, medians of 5 calls per run"}
+
+
 if __name__ == "__main__":
     rows = sys.argv[1:] or ["emit", "emit3", "inflate", "names"]
     fns = {"emit": bench_emit, "emit3": lambda: bench_emit(cfg=3), "inflate": bench_inflate,
@@ -786,5 +940,6 @@ if __name__ == "__main__":
            "inflate_fields": bench_inflate_fields,
            "http_facts": bench_http_facts,
            "inflate_http": bench_inflate_http,
+           "parse": bench_parse,
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
