@@ -846,6 +846,210 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflate
                                   int32_t *nv_verdicts, int32_t *block_http, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* Device-resident inflaters: parsed blocks into fields on the GPU        */
+/* ------------------------------------------------------------------ */
+/*
+ * The end of the chain nghttp2_amd_hd_parse_blocks_batch ->
+ * nghttp2_amd_hd_gather_literals_batch -> nghttp2_amd_hd_huff_decode_batch_auto
+ * for a caller whose wire lies in device memory: a set of HPACK decoding
+ * contexts lives in device memory across calls, and one call turns a parsed
+ * and decoded batch into nghttp2_amd_hd_nv fields and an arena in device
+ * memory, with the results of nghttp2_amd_hd_inflate_blocks -- index
+ * resolution against each connection's dynamic table, insertion with
+ * eviction, the size update rules, the sticky bad state, the fields emitted up
+ * to an error -- and advances the tables on the device.  The rules are stated
+ * once, in csrc/hd_replay.h, for the kernels and for the host twin below.
+ *
+ * One connection's header.  The HPACK numbers are exact uint32 values
+ * whatever the set's table_bytes is.
+ *   max           the table limit in force (nghttp2's hd_table_bufsize_max)
+ *   settings_max  the last nghttp2_hd_inflate_change_table_size value
+ *   min_max       the smallest such value since the last size update
+ *   size, count   the table's accounted size (32 bytes of overhead per entry)
+ *                 and its entries
+ *   head          the ring slot of the newest entry
+ *   flags         NGHTTP2_AMD_HD_DEV_EXPECT_SIZE: the next block must open with
+ *                 a size update; _BAD: a block failed, every later block
+ *                 fails with no field; _MID_BLOCK: it failed outside the wait
+ *                 for that size update, so a change of the table size is
+ *                 NGHTTP2_AMD_ERR_INVALID_STATE
+ *   cur           which of the connection's two store buffers is current
+ * A ring slot is 16 bytes: {name offset, name length | 3 << 24, value offset,
+ * value length | 3 << 24}, offsets into the connection's current store
+ * buffer; entry i (0 the newest) is slot (head + i) mod (table_bytes / 32).
+ */
+typedef struct {
+  uint32_t max, settings_max, min_max, size, count, head, flags, cur;
+} nghttp2_amd_hd_dev_conn; /* 32 bytes */
+
+#define NGHTTP2_AMD_HD_DEV_EXPECT_SIZE 0x1u
+#define NGHTTP2_AMD_HD_DEV_BAD 0x2u
+#define NGHTTP2_AMD_HD_DEV_MID_BLOCK 0x4u
+
+/* out_totals[2] of a replay: 0, or why no field was written */
+#define NGHTTP2_AMD_HD_DEV_OVERFLOW_NVA 0x1u   /* more fields than nva_cap */
+#define NGHTTP2_AMD_HD_DEV_OVERFLOW_ARENA 0x2u /* more arena bytes than arena_cap */
+#define NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 0x4u   /* a total does not fit the uint32 offsets */
+
+/*
+ * nconn decoding contexts in device memory, each as nghttp2_hd_inflate_new
+ * leaves one: maximum 4096, empty table.  Per connection the set holds the
+ * header, a ring of table_bytes / 32 entry descriptors and two byte stores of
+ * table_bytes (a call reads the entries that stay from one and writes the
+ * table it leaves to the other).  table_bytes is a power of two, at least
+ * 4096, and nconn * 2 * table_bytes at most UINT32_MAX.
+ *
+ * The capacity rule: table_bytes is the capacity per connection, not an HPACK
+ * number.  When the HPACK maximum admits an entry whose insertion would take
+ * the accounted size above table_bytes, the store cannot hold it: the block
+ * ends there with NGHTTP2_AMD_ERR_NOMEM (the reference's result when its
+ * allocation fails), the fields before it stay emitted, and the inflater
+ * turns bad.  With table_bytes >= every settings value the peer is allowed,
+ * this never happens.
+ *
+ * _new's initialisation is asynchronous on `stream`; _del frees the memory
+ * (the caller has synchronised the streams that use the set).
+ */
+typedef struct nghttp2_amd_hd_dev_inflaters nghttp2_amd_hd_dev_inflaters;
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_inflaters_new(nghttp2_amd_hd_dev_inflaters **set_ptr, uint32_t nconn,
+                                                        uint32_t table_bytes, void *stream);
+NGHTTP2_AMD_EXTERN void nghttp2_amd_hd_dev_inflaters_del(nghttp2_amd_hd_dev_inflaters *set);
+
+/*
+ * nghttp2_hd_inflate_change_table_size for n connections: request i sets
+ * connection conn[i]'s settings value to value[i] and leaves rv[i] = 0, or
+ * NGHTTP2_AMD_ERR_INVALID_STATE with nothing changed when the connection
+ * failed in the middle of a block, or NGHTTP2_AMD_ERR_INVALID_ARGUMENT for a
+ * conn[i] >= nconn.  A value below the maximum in force lowers it, evicts,
+ * and makes the next block's leading size update mandatory.  Device arrays,
+ * one lane per request, asynchronous on `stream`.  Precondition: a
+ * connection appears at most once in a call (two requests for one connection
+ * would race; issue them in two calls).
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_inflaters_change_table_size(nghttp2_amd_hd_dev_inflaters *set,
+                                                                      const uint32_t *conn, const uint32_t *value,
+                                                                      int32_t *rv, uint32_t n, void *stream);
+
+/*
+ * One connection read back, for tests and debugging (synchronises `stream`):
+ * *hdr is its header, bytes[table_bytes] its current store buffer, and
+ * entries[4 i .. 4 i + 3] = {name offset, name length, value offset, value
+ * length} into `bytes` for i < hdr->count, the newest entry first (room for
+ * table_bytes / 32 entries).  Host pointers.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_inflaters_read(nghttp2_amd_hd_dev_inflaters *set, uint32_t conn,
+                                                         nghttp2_amd_hd_dev_conn *hdr, uint32_t *entries,
+                                                         uint8_t *bytes, void *stream);
+
+/* The device workspace of nghttp2_amd_hd_dev_inflate_blocks: two counters per
+ * block, 64 bytes and a ring of table_bytes / 32 descriptors per connection
+ * (the call's insertions), and 32 bytes per record (the field references). */
+NGHTTP2_AMD_EXTERN size_t nghttp2_amd_hd_dev_inflate_workspace_size(uint32_t nconn, uint32_t table_bytes,
+                                                                    size_t ops_cap, uint32_t nblocks);
+
+/*
+ * The replay of a parsed and decoded batch against the set's connections.
+ *
+ *   wire, wire_bytes, block_off[n+1], nblocks : the batch, as the parse got it
+ *   op_off[n+1], ops, ops_cap, block_status[n], totals[4] : the parse's results
+ *   dst, dst_bytes, dst_off, status, nlits : the decode's results for the
+ *                       gathered literals: literal k is dst[dst_off[k],
+ *                       +status[k]), failed when status[k] < 0.  dst_bytes is
+ *                       dst's size (a reference past it is not read) and
+ *                       nlits the number of strings the decode was run for,
+ *                       that is, what dst_off and status hold: the parse's
+ *                       totals[1] for a complete chain.  A literal numbered
+ *                       nlits or above fails its field, so a count below
+ *                       totals[1] costs fields, never a read past the
+ *                       arrays.  With nlits == 0 none of the three is read.
+ *   conn_blk_off[nconn+1], conn_blk[nblocks] : which blocks belong to which
+ *                       connection: connection c's blocks are
+ *                       conn_blk[conn_blk_off[c], conn_blk_off[c+1]) in the
+ *                       order they are applied.  A block listed twice is the
+ *                       caller's error (its results are undefined, no memory
+ *                       outside the arrays is touched); a block not listed
+ *                       emits no field and its out_status is not written.
+ *   nva, nva_cap      : OUT: the fields, dense, in block order; `block` is the
+ *                       block's index, the offsets are positions in arena
+ *   arena, arena_cap  : OUT: name, NUL, value, NUL per field, back to back
+ *   block_nv_off[n+1] : OUT: block i's fields are nva[block_nv_off[i],
+ *                       block_nv_off[i+1])
+ *   out_status[n]     : OUT: the block's number of fields,
+ *                       NGHTTP2_AMD_ERR_HEADER_COMP (the fields before the
+ *                       error are emitted and counted in block_nv_off) or
+ *                       NGHTTP2_AMD_ERR_NOMEM (the capacity rule)
+ *   out_totals[4]     : OUT: {fields, arena bytes,
+ *                       NGHTTP2_AMD_HD_DEV_OVERFLOW_* bits, 0}
+ *   workspace         : device scratch, >= the workspace size above
+ *
+ * Per block the results are nghttp2_amd_hd_inflate_blocks' on an inflater in
+ * the same state (nghttp2_hd_inflate_hd3 with in_final, then
+ * nghttp2_hd_inflate_end_headers): a block whose parse status is
+ * NGHTTP2_AMD_ERR_HEADER_COMP fails behind its completed records, a literal
+ * whose decode status is negative fails its field (the name is examined
+ * before the value), index 0 or an index past 61 + entries fails, an entry
+ * larger than the maximum empties the table and is not inserted.
+ *
+ * Overflow is all or nothing.  When the batch emits more fields than nva_cap
+ * or more bytes than arena_cap, out_totals holds the sizes needed with the
+ * bits set, nothing is written to nva or arena, and the tables are as before
+ * the call: repeat it with room.  block_nv_off and out_status are valid
+ * either way (not with OVERFLOW_U32).  nva_cap = ops_cap, or the parse's
+ * totals[0], cannot overflow; the arena has no useful a-priori bound (an
+ * indexed field of one wire byte emits its entry's bytes).
+ *
+ * A clear of the block counters and four launches: k_replay (one lane per
+ * connection walks its blocks; no byte moves: every name and value is a
+ * reference into the static table, the wire, the decode's output or the
+ * connection's store), a one-workgroup scan, k_emit (a wave per 64 records:
+ * the nghttp2_amd_hd_nv of each, then the strings with the lanes on
+ * consecutive bytes) and k_commit (a wave per connection that had blocks
+ * rewrites its table into its other store buffer).  k_emit's grid covers
+ * ops_cap records, because the count is known on the device only: a workgroup
+ * past the parse's totals[0] returns at once, and an ops_cap close to the
+ * batch's records is cheaper than the parse's bound.  The counts are read from
+ * totals on the device, so the call follows parse, gather and decode on the
+ * stream with no host synchronisation; it does nothing when totals[3] is not
+ * 0 on entry.
+ *
+ * Device pointers, asynchronous on `stream`; calls on one set are ordered by
+ * the caller (one stream, or events).  nblocks == 0 returns 0 and touches
+ * nothing.  A NULL set, wire, block_off, op_off, ops, block_status, totals,
+ * dst, dst_off, status, conn_blk_off, conn_blk, nva (with nva_cap > 0), arena
+ * (with arena_cap > 0), block_nv_off, out_status, out_totals or workspace, or
+ * a workspace below the size above, is NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_inflate_blocks(
+    nghttp2_amd_hd_dev_inflaters *set, const uint8_t *wire, size_t wire_bytes, const uint32_t *block_off,
+    uint32_t nblocks, const uint32_t *op_off, const nghttp2_amd_hd_op *ops, size_t ops_cap,
+    const int32_t *block_status, const uint32_t *totals, const uint8_t *dst, size_t dst_bytes,
+    const uint32_t *dst_off, const int32_t *status, uint32_t nlits, const uint32_t *conn_blk_off,
+    const uint32_t *conn_blk, nghttp2_amd_hd_nv *nva, size_t nva_cap, uint8_t *arena, size_t arena_cap, uint32_t *block_nv_off,
+    int32_t *out_status, uint32_t *out_totals, void *workspace, size_t ws_bytes, void *stream);
+
+/*
+ * The host twin (no GPU call): the same walk over host arrays with the same
+ * layouts, for ONE connection whose blocks are the batch's, in order.  hdr is
+ * the connection's header (nghttp2_amd_hd_replay_host_init makes a fresh
+ * one), ring its table_bytes / 32 slots of 16 bytes, store its two buffers
+ * (2 * table_bytes).  ops[op_off[i], op_off[i+1]) are block i's records with
+ * offsets into wire; nlits bounds the literal numbers (dst, dst_off and
+ * status may be NULL when it is 0; hdr, ring, store, wire, ops and the offset
+ * and output arrays may not).  Outputs, the overflow rule and the commit
+ * are the device call's.  _change_table_size is one request of the device
+ * call's, returning its rv.
+ */
+NGHTTP2_AMD_EXTERN void nghttp2_amd_hd_replay_host_init(nghttp2_amd_hd_dev_conn *hdr);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_replay_host_change_table_size(nghttp2_amd_hd_dev_conn *hdr, const void *ring,
+                                                                    uint32_t table_bytes, uint32_t value);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_replay_host(
+    nghttp2_amd_hd_dev_conn *hdr, void *ring, uint8_t *store, uint32_t table_bytes, const uint8_t *wire,
+    size_t wire_bytes, const uint32_t *block_off, uint32_t nblocks, const uint32_t *op_off,
+    const nghttp2_amd_hd_op *ops, const int32_t *block_status, const uint8_t *dst, const uint32_t *dst_off,
+    const int32_t *status, uint32_t nlits, nghttp2_amd_hd_nv *nva, size_t nva_cap, uint8_t *arena,
+    size_t arena_cap, uint32_t *block_nv_off, int32_t *out_status, uint32_t *out_totals);
+
+/* ------------------------------------------------------------------ */
 /* Batched HPACK deflate front-end                                      */
 /* ------------------------------------------------------------------ */
 /*

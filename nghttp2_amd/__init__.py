@@ -16,6 +16,8 @@ from .hd import (  # noqa: F401
     CHECK_PATH,
     CHECK_VALUE,
     CHECK_VALUE_RFC9113,
+    DeviceInflaters,
+    HostReplayInflater,
     HpackDeflater,
     HpackInflater,
     HuffmanBatchCodec,
@@ -24,12 +26,14 @@ from .hd import (  # noqa: F401
     NGHTTP2_ERR_INVALID_STATE,
     NGHTTP2_ERR_INSUFF_BUFSIZE,
     NGHTTP2_ERR_INVALID_ARGUMENT,
+    NGHTTP2_ERR_NOMEM,
     TOKEN_INVALID,
     TOKEN_NONE,
     check_field,
     decode_length,
     lib,
     parse_block,
+    replay_fields,
     lib_path,
     deflate_blocks,
     inflate_blocks,

@@ -1,6 +1,6 @@
 // hd_host.h -- what the host layers above the C ABI share (hd_inflate.cpp,
-// hd_deflate.cpp, hd_sharded.cpp): the HPACK static table with its lengths
-// computed at compile time, the HIP error reports (hip_rv is the kernel
+// hd_deflate.cpp, hd_sharded.cpp): the HPACK static table (hd_static.h), the
+// HIP error reports (hip_rv is the kernel
 // layers' own, the .hip files'), and the growable device and pinned host
 // buffers the layers stage their batches in.
 #pragma once
@@ -11,54 +11,11 @@
 #include <stdio.h>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_static.h"
 #include "hd_tokens.h"
 
 namespace hdhost {
 
-constexpr uint32_t kEntryOverhead = 32;  // NGHTTP2_HD_ENTRY_OVERHEAD
-constexpr uint32_t kStaticLen = 61;
-// RFC 7541 Appendix A
-constexpr const char *kStatic[kStaticLen][2] = {
-    {":authority", ""}, {":method", "GET"}, {":method", "POST"}, {":path", "/"},
-    {":path", "/index.html"}, {":scheme", "http"}, {":scheme", "https"}, {":status", "200"},
-    {":status", "204"}, {":status", "206"}, {":status", "304"}, {":status", "400"},
-    {":status", "404"}, {":status", "500"}, {"accept-charset", ""},
-    {"accept-encoding", "gzip, deflate"}, {"accept-language", ""}, {"accept-ranges", ""},
-    {"accept", ""}, {"access-control-allow-origin", ""}, {"age", ""}, {"allow", ""},
-    {"authorization", ""}, {"cache-control", ""}, {"content-disposition", ""},
-    {"content-encoding", ""}, {"content-language", ""}, {"content-length", ""},
-    {"content-location", ""}, {"content-range", ""}, {"content-type", ""}, {"cookie", ""},
-    {"date", ""}, {"etag", ""}, {"expect", ""}, {"expires", ""}, {"from", ""}, {"host", ""},
-    {"if-match", ""}, {"if-modified-since", ""}, {"if-none-match", ""}, {"if-range", ""},
-    {"if-unmodified-since", ""}, {"last-modified", ""}, {"link", ""}, {"location", ""},
-    {"max-forwards", ""}, {"proxy-authenticate", ""}, {"proxy-authorization", ""},
-    {"range", ""}, {"referer", ""}, {"refresh", ""}, {"retry-after", ""}, {"server", ""},
-    {"set-cookie", ""}, {"strict-transport-security", ""}, {"transfer-encoding", ""},
-    {"user-agent", ""}, {"vary", ""}, {"via", ""}, {"www-authenticate", ""}};
-
-// The entries' lengths ([i][0] name, [i][1] value), and the longest of each.
-struct StaticLens {
-  uint32_t len[kStaticLen][2];
-  uint32_t max[2];
-};
-constexpr StaticLens make_static_lens() {
-  StaticLens t{};
-  for (uint32_t i = 0; i < kStaticLen; ++i)
-    for (int w = 0; w < 2; ++w) {
-      t.len[i][w] = hdtok::cstr_len(kStatic[i][w]);
-      if (t.len[i][w] > t.max[w]) t.max[w] = t.len[i][w];
-    }
-  return t;
-}
-constexpr StaticLens kStaticLens = make_static_lens();
-static_assert(kStaticLens.max[0] == 27 && kStaticLens.max[1] == 13, "access-control-allow-origin, gzip, deflate");
-// static entry idx (0-based, < kStaticLen)
-inline void static_entry(uint32_t idx, const char **name, size_t *nl, const char **value, size_t *vl) {
-  *name = kStatic[idx][0];
-  *nl = kStaticLens.len[idx][0];
-  *value = kStatic[idx][1];
-  *vl = kStaticLens.len[idx][1];
-}
 // `what` names the failed call; the sharded engine, which names none, passes nullptr
 inline bool hip_ok(hipError_t e, const char *layer, const char *what) {
   if (e == hipSuccess) return true;

@@ -38,11 +38,16 @@
 #include "../../include/nghttp2_amd_hd.h"
 #include "hd_host.h"
 #include "hd_parse.h"
+#include "hd_scan.h"
 
 namespace {
 
+using hdscan::SC_WG;
+using hdscan::Share;
+using hdscan::scan_sums;
+using hdscan::scan_write;
+
 constexpr uint32_t PB_WG = 64;    // k_parse_blocks: one wave, 64 blocks (latency bound: many small workgroups)
-constexpr uint32_t SC_WG = 1024;  // the scans: one workgroup
 constexpr uint32_t GL_WG = 256;   // k_lit_lens, k_gather
 
 // a record into ops[base + k], when that is a place below cap
@@ -83,65 +88,6 @@ __global__ __launch_bounds__(PB_WG) void k_parse_blocks(const uint8_t *__restric
   }
 }
 
-// The exclusive prefix of x[0, n) in place, by one workgroup of SC_WG threads
-// (k_tile_prefix64's scheme: a thread owns a contiguous share, the shares'
-// sums are scanned across the wave and the waves' sums through LDS).
-// scan_sums leaves the thread's share [b, e) and the sum before it and
-// returns the total; scan_write stores the prefixes and x[n] = the total.
-struct Share {
-  uint32_t b, e;
-  uint64_t run;
-};
-__device__ __forceinline__ uint64_t scan_sums(const uint32_t *x, uint32_t n, uint64_t *wsum, Share *sh) {
-  const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-  const uint32_t per = n / SC_WG + (n % SC_WG ? 1u : 0u);
-  const uint32_t b = min(t * per, n), e = min(b + per, n);
-  uint64_t s = 0;
-  // (the share's loads are independent: unrolled, eight are in flight at a
-  // time -- one by one, their latency was the whole kernel: DESIGN.md 2.12)
-#pragma unroll 8
-  for (uint32_t i = b; i < e; ++i) s += x[i];
-  uint64_t inc = s;
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) {
-    const uint64_t v = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += v;
-  }
-  if (lane == 63u) wsum[wv] = inc;
-  __syncthreads();
-  uint64_t run = inc - s, total = 0;
-  for (uint32_t w = 0; w < SC_WG / 64u; ++w) {
-    if (w < wv) run += wsum[w];
-    total += wsum[w];
-  }
-  sh->b = b;
-  sh->e = e;
-  sh->run = run;
-  return total;
-}
-__device__ __forceinline__ void scan_write(uint32_t *x, uint32_t n, const Share &sh, uint64_t total) {
-  uint64_t run = sh.run;
-  uint32_t i = sh.b;
-  // (a thread reads x[i] before it stores there, and only its share; eight
-  // loads ahead of the eight stores)
-  for (; i + 8u <= sh.e; i += 8u) {
-    uint32_t v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = x[i + k];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      x[i + k] = (uint32_t)run;
-      run += v[k];
-    }
-  }
-  for (; i < sh.e; ++i) {
-    const uint32_t v = x[i];
-    x[i] = (uint32_t)run;
-    run += v;
-  }
-  if (threadIdx.x == 0) x[n] = (uint32_t)total;
-}
-
 __global__ __launch_bounds__(SC_WG) void k_parse_scan(uint32_t *__restrict__ op_off, uint32_t *__restrict__ lit_base,
                                                       uint32_t *__restrict__ byte_base, uint32_t n, uint32_t ops_cap,
                                                       uint32_t *__restrict__ totals) {
@@ -152,9 +98,9 @@ __global__ __launch_bounds__(SC_WG) void k_parse_scan(uint32_t *__restrict__ op_
   const uint64_t t2 = scan_sums(byte_base, n, wsum[2], &s2);
   const bool wide = ((t0 | t1 | t2) >> 32) != 0;
   if (!wide) {
-    scan_write(op_off, n, s0, t0);
-    scan_write(lit_base, n, s1, t1);
-    scan_write(byte_base, n, s2, t2);
+    scan_write(op_off, op_off, n, s0, t0);
+    scan_write(lit_base, lit_base, n, s1, t1);
+    scan_write(byte_base, byte_base, n, s2, t2);
   }
   if (threadIdx.x == 0) {
     totals[0] = wide ? 0xFFFFFFFFu : (uint32_t)t0;
@@ -195,7 +141,7 @@ __global__ __launch_bounds__(SC_WG) void k_lit_scan(uint32_t *__restrict__ total
     if (threadIdx.x == 0) totals[3] = NGHTTP2_AMD_HD_PARSE_OVERFLOW_U32;
     return;
   }
-  scan_write(lit_off, T, sh, P);
+  scan_write(lit_off, lit_off, T, sh, P);
   if (threadIdx.x == 0 && P > pool_cap) totals[3] = NGHTTP2_AMD_HD_PARSE_OVERFLOW_POOL;
 }
 

@@ -1,0 +1,574 @@
+// hd_replay.hip -- device-resident HPACK inflaters: parsed blocks into fields, for gfx950.
+//
+// Reference: the table half of nghttp2_hd_inflate_hd_nv (hd_replay.h, the one
+// statement of the walk, shared with the host twin below).  A set of decoding
+// contexts lives in device memory: per connection a 32-byte header, a ring of
+// table_bytes / 32 entry descriptors and two byte stores of table_bytes.
+//
+// nghttp2_amd_hd_dev_inflate_blocks, one clear of 2 (n + 1) counters and four
+// launches behind parse -> gather -> decode:
+//   k_replay       one lane per connection, 64 connections per one-wave
+//                  workgroup: the lane walks its connection's blocks in order
+//                  and leaves one FieldRef per record, the blocks' field
+//                  counts, arena bytes and statuses, and the table as the
+//                  call leaves it (header, the ring of this call's
+//                  insertions) in the workspace.  Serial, dependent loads at
+//                  per-lane addresses: a latency, not a bandwidth.  No LDS.
+//   k_replay_scan  one workgroup (hd_scan.h): block_nv_off, the blocks' arena
+//                  bases, out_totals with the overflow bits.
+//   k_emit         a wave per 64 consecutive records: each lane writes its
+//                  field's nghttp2_amd_hd_nv, then the wave copies the fields'
+//                  name, NUL, value, NUL one after the other with its lanes
+//                  on consecutive bytes (k_gather's shape).
+//   k_commit       a wave per connection that had blocks: the live entries'
+//                  bytes go back to back into the connection's other store
+//                  buffer, their descriptors become table references, and the
+//                  header is written back with the current-buffer bit flipped.
+// With an overflow bit in out_totals[2], k_emit and k_commit do nothing: no
+// field is written and every table is as before the call.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <vector>
+
+#include "../../include/nghttp2_amd_hd.h"
+#include "hd_host.h"
+#include "hd_replay.h"
+#include "hd_scan.h"
+
+struct nghttp2_amd_hd_dev_inflaters {
+  uint32_t nconn, table_bytes;
+  hdreplay::Conn *hdr;    // [nconn]
+  hdreplay::Entry *ring;  // [nconn][table_bytes / 32]
+  uint8_t *store;         // [nconn][2][table_bytes]
+};
+
+namespace {
+
+using hdreplay::Conn;
+using hdreplay::Entry;
+using hdreplay::FieldRef;
+using hdreplay::Ref;
+using hdscan::SC_WG;
+
+constexpr uint32_t RP_WG = 64;   // k_replay, k_change_size, k_init: one wave, 64 connections
+constexpr uint32_t EM_WG = 256;  // k_emit: four waves, 64 records each
+constexpr uint32_t CM_WG = 64;   // k_commit: one wave, one connection
+
+__constant__ hdhost::StaticPool d_static = hdhost::kStaticPool;
+
+// What k_replay leaves k_commit for a connection that had blocks.
+struct Left {  // 64 bytes
+  Conn h;
+  uint32_t nnew, nhead, nold, walked;
+  uint32_t pad[4];
+};
+
+// The workspace: blk_count[n + 1], blk_bytes[n + 1] (cleared by the call),
+// left[nconn], fresh[nconn][slots], fref[ops_cap].
+struct Ws {
+  uint32_t *blk_count, *blk_bytes;
+  Left *left;
+  Entry *fresh;
+  FieldRef *fref;
+  size_t clear_bytes, total;
+};
+__host__ Ws ws_layout(void *base, uint32_t nconn, uint32_t table_bytes, size_t ops_cap, uint32_t n) {
+  Ws w;
+  uint8_t *p = (uint8_t *)base;
+  size_t at = 0;
+  w.blk_count = (uint32_t *)(p + at);
+  at += ((size_t)n + 1u) * sizeof(uint32_t);
+  w.blk_bytes = (uint32_t *)(p + at);
+  at += ((size_t)n + 1u) * sizeof(uint32_t);
+  w.clear_bytes = at;
+  at = hdhost::round16(at);
+  w.left = (Left *)(p + at);
+  at += (size_t)nconn * sizeof(Left);
+  w.fresh = (Entry *)(p + at);
+  at += (size_t)nconn * (table_bytes / hdreplay::kOverhead) * sizeof(Entry);
+  w.fref = (FieldRef *)(p + at);
+  at += ops_cap * sizeof(FieldRef);
+  w.total = at;
+  return w;
+}
+
+struct FrefStore {
+  FieldRef *fref;
+  uint32_t base, cap;
+  __device__ void operator()(uint32_t k, const FieldRef &fr) const {
+    const uint32_t idx = base + k;
+    if (idx >= base && idx < cap) fref[idx] = fr;
+  }
+};
+
+__global__ __launch_bounds__(RP_WG) void k_init(Conn *__restrict__ hdr, uint32_t nconn) {
+  const uint32_t c = blockIdx.x * RP_WG + threadIdx.x;
+  if (c >= nconn) return;
+  Conn h;
+  hdreplay::conn_init(&h);
+  hdr[c] = h;
+}
+
+__global__ __launch_bounds__(RP_WG) void k_change_size(Conn *__restrict__ hdr, const Entry *__restrict__ ring,
+                                                       uint32_t nconn, uint32_t table_bytes,
+                                                       const uint32_t *__restrict__ conn,
+                                                       const uint32_t *__restrict__ value, int32_t *__restrict__ rv,
+                                                       uint32_t n) {
+  const uint32_t i = blockIdx.x * RP_WG + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = conn[i];
+  if (c >= nconn) {
+    rv[i] = NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+    return;
+  }
+  Conn h = hdr[c];
+  rv[i] = hdreplay::change_table_size(&h, ring + (size_t)c * (table_bytes / hdreplay::kOverhead), table_bytes, value[i]);
+  hdr[c] = h;
+}
+
+__global__ __launch_bounds__(RP_WG) void k_replay(
+    const Conn *__restrict__ hdr, const Entry *__restrict__ ring, uint32_t nconn, uint32_t table_bytes,
+    const uint8_t *__restrict__ wire, uint64_t wire_bytes, const uint32_t *__restrict__ block_off, uint32_t n,
+    const uint32_t *__restrict__ op_off, const nghttp2_amd_hd_op *__restrict__ ops, uint32_t ops_cap,
+    const int32_t *__restrict__ block_status, const uint32_t *__restrict__ totals,
+    const uint32_t *__restrict__ dst_off, const int32_t *__restrict__ status, uint32_t nlits,
+    const uint32_t *__restrict__ conn_blk_off, const uint32_t *__restrict__ conn_blk, int32_t *__restrict__ out_status,
+    uint32_t *__restrict__ blk_count, uint32_t *__restrict__ blk_bytes, Left *__restrict__ left,
+    Entry *__restrict__ fresh, FieldRef *__restrict__ fref) {
+  const uint32_t c = blockIdx.x * RP_WG + threadIdx.x;
+  if (c >= nconn) return;
+  const uint32_t b0 = conn_blk_off[c], b1 = min(conn_blk_off[c + 1], n);
+  if (b0 >= b1) {  // a connection without blocks
+    left[c].walked = 0u;
+    return;
+  }
+  if (totals[3]) return;  // the parse's results are not complete
+  const uint32_t nops = min(totals[0], ops_cap);
+  const uint32_t slots = table_bytes / hdreplay::kOverhead;
+  const Conn h0 = hdr[c];
+  hdreplay::Table t;
+  hdreplay::table_open(&t, h0, ring + (size_t)c * slots, fresh + (size_t)c * slots, table_bytes,
+                       (2u * c + (h0.cur & 1u)) * table_bytes);
+  const hdreplay::Lits lits = {dst_off, status, min(totals[1], nlits)};  // (never past the decode's arrays)
+  for (uint32_t j = b0; j < b1; ++j) {
+    const uint32_t b = conn_blk[j];
+    if (b >= n) continue;
+    const uint32_t r0 = min(op_off[b], nops), r1 = min(op_off[b + 1], nops);
+    const uint32_t w0 = block_off[b], w1 = block_off[b + 1];
+    const bool first_is_size = w0 < w1 && w0 < wire_bytes && (wire[w0] & 0xE0u) == 0x20u;
+    const hdreplay::BlockResult r =
+        hdreplay::walk_block(&t, b, ops + r0, r1 > r0 ? r1 - r0 : 0u, block_status[b] >= 0, first_is_size, lits,
+                             &d_static, FrefStore{fref, r0, ops_cap});
+    out_status[b] = r.status;
+    blk_count[b] = r.fields;
+    blk_bytes[b] = r.bytes;
+  }
+  Left l;
+  l.h = t.h;
+  l.nnew = t.nnew;
+  l.nhead = t.nhead;
+  l.nold = t.nold;
+  l.walked = 1u;
+  l.pad[0] = l.pad[1] = l.pad[2] = l.pad[3] = 0u;
+  left[c] = l;
+}
+
+__global__ __launch_bounds__(SC_WG) void k_replay_scan(const uint32_t *__restrict__ totals,
+                                                       const uint32_t *blk_count, uint32_t *blk_bytes, uint32_t n,
+                                                       uint32_t nva_cap, uint32_t arena_cap,
+                                                       uint32_t *block_nv_off, uint32_t *__restrict__ out_totals) {
+  __shared__ uint64_t wsum[2][SC_WG / 64];
+  if (totals[3]) return;
+  hdscan::Share s0, s1;
+  const uint64_t t0 = hdscan::scan_sums(blk_count, n, wsum[0], &s0);
+  const uint64_t t1 = hdscan::scan_sums(blk_bytes, n, wsum[1], &s1);
+  const bool wide = ((t0 | t1) >> 32) != 0;
+  if (!wide) {
+    hdscan::scan_write(blk_count, block_nv_off, n, s0, t0);
+    hdscan::scan_write(blk_bytes, blk_bytes, n, s1, t1);
+  }
+  if (threadIdx.x == 0) {
+    out_totals[0] = wide ? 0xFFFFFFFFu : (uint32_t)t0;
+    out_totals[1] = wide ? 0xFFFFFFFFu : (uint32_t)t1;
+    out_totals[2] = (wide ? NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 : 0u) | (t0 > nva_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_NVA : 0u) |
+                    (t1 > arena_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_ARENA : 0u);
+    out_totals[3] = 0u;
+  }
+}
+
+// The four stores a Ref can name, with their sizes: a Ref that reaches past
+// its store is not read.
+struct Stores {
+  const uint8_t *base[4];
+  uint64_t bytes[4];
+};
+__device__ __forceinline__ bool ref_ok(const Stores &s, Ref r) {
+  const uint32_t src = hdreplay::ref_src(r);  // (selected, not indexed: the struct stays in registers)
+  const uint64_t lim = src == hdreplay::SRC_STATIC ? s.bytes[0]
+                       : src == hdreplay::SRC_WIRE ? s.bytes[1]
+                       : src == hdreplay::SRC_POOL ? s.bytes[2]
+                       : src == hdreplay::SRC_TABLE ? s.bytes[3]
+                                                    : 0u;
+  return (uint64_t)r.off + hdreplay::ref_len(r) <= lim;
+}
+// The wave copies the strings of the lanes with `has`, one after the other,
+// its lanes on consecutive bytes: lane l's is r's bytes to out[d, ...), with a
+// NUL behind it when nul.  Every store is below cap.
+__device__ __forceinline__ void wave_copy(const Stores &s, bool has, Ref r, uint64_t d, uint8_t *out, uint64_t cap,
+                                          bool nul, uint32_t lane) {
+  uint64_t m = __ballot(has);
+  while (m) {
+    const int l = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)r.off, l);
+    const uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)r.ls, l);
+    const uint32_t dlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)d, l);
+    const uint32_t dhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(d >> 32), l);
+    const uint64_t to = ((uint64_t)dhi << 32) | dlo;
+    const uint32_t nb = ls & 0xFFFFFFu, src = ls >> 24;
+    const uint8_t *from = (src == hdreplay::SRC_STATIC ? s.base[0]
+                           : src == hdreplay::SRC_WIRE ? s.base[1]
+                           : src == hdreplay::SRC_POOL ? s.base[2]
+                                                       : s.base[3]) + off;
+    for (uint32_t b = lane; b < nb; b += 64u)
+      if (to + b < cap) out[to + b] = from[b];
+    if (nul && lane == 0u && to + nb < cap) out[to + nb] = 0u;
+  }
+}
+
+__global__ __launch_bounds__(EM_WG) void k_emit(Stores stores, const uint32_t *__restrict__ totals,
+                                                const uint32_t *__restrict__ op_off, uint32_t n, uint32_t ops_cap,
+                                                const FieldRef *__restrict__ fref,
+                                                const uint32_t *__restrict__ block_nv_off,
+                                                const uint32_t *__restrict__ arena_base,
+                                                const uint32_t *__restrict__ out_totals,
+                                                nghttp2_amd_hd_nv *__restrict__ nva, uint32_t nva_cap,
+                                                uint8_t *__restrict__ arena, uint32_t arena_cap) {
+  if (totals[3] || out_totals[2]) return;
+  stores.base[0] = d_static.bytes;
+  const uint32_t nops = min(totals[0], ops_cap);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t t0 = (blockIdx.x * (EM_WG / 64u) + (threadIdx.x >> 6)) * 64u;  // the wave's records
+  if (t0 >= nops) return;
+  const uint32_t r = t0 + lane;
+  FieldRef fr = {};
+  fr.block = hdreplay::kNoField;
+  if (r < nops) fr = fref[r];
+  // a field of a block the walk covered: the record lies in its block and the
+  // ordinal below the block's count (a block no connection lists counts 0)
+  bool has = fr.block < n;
+  uint32_t idx = 0, at = 0;
+  if (has) {
+    const uint32_t f0 = block_nv_off[fr.block], f1 = block_nv_off[fr.block + 1];
+    has = r >= op_off[fr.block] && r < op_off[fr.block + 1] && fr.ordinal < f1 - f0 && ref_ok(stores, fr.name) &&
+          ref_ok(stores, fr.value);
+    idx = f0 + fr.ordinal;
+    at = arena_base[fr.block] + fr.before;
+    has = has && idx < nva_cap;
+  }
+  const uint32_t nl = hdreplay::ref_len(fr.name), vl = hdreplay::ref_len(fr.value);
+  if (has) {
+    nghttp2_amd_hd_nv nv = {};
+    nv.block = fr.block;
+    nv.name_off = at;
+    nv.name_len = nl;
+    nv.value_off = at + nl + 1u;
+    nv.value_len = vl;
+    nv.flags = (uint8_t)fr.flags;
+    nva[idx] = nv;
+  }
+  wave_copy(stores, has, fr.name, at, arena, arena_cap, true, lane);
+  wave_copy(stores, has, fr.value, (uint64_t)at + nl + 1u, arena, arena_cap, true, lane);
+}
+
+__global__ __launch_bounds__(CM_WG) void k_commit(Stores stores, const uint32_t *__restrict__ totals,
+                                                  const uint32_t *__restrict__ out_totals,
+                                                  const Left *__restrict__ left, const Entry *__restrict__ fresh,
+                                                  Conn *__restrict__ hdr, Entry *ring, uint8_t *store,
+                                                  uint32_t table_bytes) {
+  if (totals[3] || out_totals[2]) return;
+  const uint32_t c = blockIdx.x, lane = threadIdx.x;
+  const Left l = left[c];
+  if (!l.walked) return;
+  stores.base[0] = d_static.bytes;
+  const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
+  Entry *cring = ring + (size_t)c * slots;
+  const Entry *cfresh = fresh + (size_t)c * slots;
+  const uint32_t cur = l.h.cur & 1u, other = cur ^ 1u;
+  const uint32_t cur_off = (2u * c + cur) * table_bytes;
+  uint8_t *to = store + (size_t)(2u * c + other) * table_bytes;
+  const uint32_t count = l.nnew + l.nold;
+  const uint32_t head = (l.h.head - l.nnew) & mask;
+  // The slots of the entries that stay, ring[h.head + j], are the slots they
+  // end in, head + nnew + j: a lane reads the descriptor it then replaces,
+  // and the fresh entries go in front of them, into slots no live entry has.
+  uint32_t run = 0;
+  for (uint32_t i0 = 0; i0 < count; i0 += 64u) {
+    const uint32_t i = i0 + lane;
+    const bool live = i < count;
+    Entry e = {};
+    if (live) {
+      if (i < l.nnew) {
+        e = cfresh[(l.nhead + i) & mask];
+      } else {
+        e = cring[(l.h.head + (i - l.nnew)) & mask];
+        e.name.off += cur_off;
+        e.value.off += cur_off;
+      }
+    }
+    const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
+    const bool ok = live && ref_ok(stores, e.name) && ref_ok(stores, e.value);
+    const uint32_t len = ok ? nl + vl : 0u;
+    uint32_t inc = len;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t v = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += v;
+    }
+    const uint32_t at = run + inc - len;
+    const bool fits = ok && (uint64_t)at + len <= table_bytes;
+    wave_copy(stores, fits, e.name, at, to, table_bytes, false, lane);
+    wave_copy(stores, fits, e.value, (uint64_t)at + nl, to, table_bytes, false, lane);
+    if (live) {
+      Entry d;
+      d.name = hdreplay::make_ref(hdreplay::SRC_TABLE, at, fits ? nl : 0u);
+      d.value = hdreplay::make_ref(hdreplay::SRC_TABLE, at + (fits ? nl : 0u), fits ? vl : 0u);
+      cring[(head + i) & mask] = d;
+    }
+    run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+  }
+  if (lane == 0u) {
+    Conn h = l.h;
+    h.head = head;
+    h.count = count;
+    h.cur = other;
+    hdr[c] = h;
+  }
+}
+
+uint32_t clamp32(size_t x) { return x > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)x; }
+bool table_bytes_ok(uint32_t tb) { return tb >= 4096u && (tb & (tb - 1u)) == 0u; }
+
+}  // namespace
+
+extern "C" {
+
+int nghttp2_amd_hd_dev_inflaters_new(nghttp2_amd_hd_dev_inflaters **set_ptr, uint32_t nconn, uint32_t table_bytes,
+                                     void *stream) {
+  // (a table reference is a uint32 offset into the set's store allocation)
+  if (!set_ptr || nconn == 0 || !table_bytes_ok(table_bytes) || (uint64_t)nconn * 2u * table_bytes > 0xFFFFFFFFull)
+    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  nghttp2_amd_hd_dev_inflaters *s = new (std::nothrow) nghttp2_amd_hd_dev_inflaters();
+  if (!s) return NGHTTP2_AMD_ERR_NOMEM;
+  s->nconn = nconn;
+  s->table_bytes = table_bytes;
+  const size_t slots = table_bytes / hdreplay::kOverhead;
+  if (hipMalloc((void **)&s->hdr, (size_t)nconn * sizeof(Conn)) != hipSuccess ||
+      hipMalloc((void **)&s->ring, (size_t)nconn * slots * sizeof(Entry)) != hipSuccess ||
+      hipMalloc((void **)&s->store, (size_t)nconn * 2u * table_bytes) != hipSuccess) {
+    nghttp2_amd_hd_dev_inflaters_del(s);
+    return NGHTTP2_AMD_ERR_NOMEM;
+  }
+  hipLaunchKernelGGL(k_init, dim3((nconn + RP_WG - 1u) / RP_WG), dim3(RP_WG), 0, (hipStream_t)stream, s->hdr, nconn);
+  const int rv = hdhost::hip_rv(hipGetLastError());
+  if (rv) {
+    nghttp2_amd_hd_dev_inflaters_del(s);
+    return rv;
+  }
+  *set_ptr = s;
+  return 0;
+}
+
+void nghttp2_amd_hd_dev_inflaters_del(nghttp2_amd_hd_dev_inflaters *set) {
+  if (!set) return;
+  if (set->hdr) (void)hipFree(set->hdr);
+  if (set->ring) (void)hipFree(set->ring);
+  if (set->store) (void)hipFree(set->store);
+  delete set;
+}
+
+int nghttp2_amd_hd_dev_inflaters_change_table_size(nghttp2_amd_hd_dev_inflaters *set, const uint32_t *conn,
+                                                   const uint32_t *value, int32_t *rv, uint32_t n, void *stream) {
+  if (n == 0) return 0;
+  if (!set || !conn || !value || !rv) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(k_change_size, dim3((n + RP_WG - 1u) / RP_WG), dim3(RP_WG), 0, (hipStream_t)stream, set->hdr,
+                     (const Entry *)set->ring, set->nconn, set->table_bytes, conn, value, rv, n);
+  return hdhost::hip_rv(hipGetLastError());
+}
+
+int nghttp2_amd_hd_dev_inflaters_read(nghttp2_amd_hd_dev_inflaters *set, uint32_t conn, nghttp2_amd_hd_dev_conn *hdr,
+                                      uint32_t *entries, uint8_t *bytes, void *stream) {
+  if (!set || conn >= set->nconn || !hdr || !entries || !bytes) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t tb = set->table_bytes, slots = tb / hdreplay::kOverhead;
+  std::vector<Entry> ring(slots);
+  hipError_t e = hipMemcpyAsync(hdr, set->hdr + conn, sizeof(Conn), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(ring.data(), set->ring + (size_t)conn * slots, slots * sizeof(Entry), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(bytes, set->store + (size_t)(2u * conn + (hdr->cur & 1u)) * tb, tb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hdhost::hip_rv(e);
+  if (hdr->count > slots) return NGHTTP2_AMD_ERR_FATAL;
+  for (uint32_t i = 0; i < hdr->count; ++i) {
+    const Entry d = ring[(hdr->head + i) & (slots - 1u)];
+    entries[4 * i + 0] = d.name.off;
+    entries[4 * i + 1] = hdreplay::ref_len(d.name);
+    entries[4 * i + 2] = d.value.off;
+    entries[4 * i + 3] = hdreplay::ref_len(d.value);
+  }
+  return 0;
+}
+
+size_t nghttp2_amd_hd_dev_inflate_workspace_size(uint32_t nconn, uint32_t table_bytes, size_t ops_cap,
+                                                 uint32_t nblocks) {
+  return ws_layout(nullptr, nconn, table_bytes, ops_cap, nblocks).total;
+}
+
+int nghttp2_amd_hd_dev_inflate_blocks(nghttp2_amd_hd_dev_inflaters *set, const uint8_t *wire, size_t wire_bytes,
+                                      const uint32_t *block_off, uint32_t nblocks, const uint32_t *op_off,
+                                      const nghttp2_amd_hd_op *ops, size_t ops_cap, const int32_t *block_status,
+                                      const uint32_t *totals, const uint8_t *dst, size_t dst_bytes,
+                                      const uint32_t *dst_off, const int32_t *status, uint32_t nlits,
+                                      const uint32_t *conn_blk_off, const uint32_t *conn_blk,
+                                      nghttp2_amd_hd_nv *nva, size_t nva_cap, uint8_t *arena, size_t arena_cap,
+                                      uint32_t *block_nv_off, int32_t *out_status, uint32_t *out_totals,
+                                      void *workspace, size_t ws_bytes, void *stream) {
+  const uint32_t n = nblocks;
+  if (n == 0) return 0;
+  if (!set || !wire || !block_off || !op_off || !ops || !block_status || !totals || !dst || !dst_off || !status ||
+      !conn_blk_off || !conn_blk || (!nva && nva_cap) || (!arena && arena_cap) || !block_nv_off || !out_status ||
+      !out_totals || !workspace)
+    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  const uint32_t cap = clamp32(ops_cap), nconn = set->nconn, tb = set->table_bytes;
+  const Ws w = ws_layout(workspace, nconn, tb, cap, n);
+  if (ws_bytes < w.total) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  hipStream_t st = (hipStream_t)stream;
+  Stores stores;
+  stores.base[0] = nullptr;  // the kernels' own constant pool
+  stores.bytes[0] = hdhost::kStaticPoolBytes;
+  stores.base[1] = wire;
+  stores.bytes[1] = wire_bytes;
+  stores.base[2] = dst;
+  stores.bytes[2] = dst_bytes;
+  stores.base[3] = set->store;
+  stores.bytes[3] = (uint64_t)nconn * 2u * tb;
+  // (a block no connection lists counts no field and no byte)
+  hipError_t e = hipMemsetAsync(w.blk_count, 0, w.clear_bytes, st);
+  if (e != hipSuccess) return hdhost::hip_rv(e);
+  hipLaunchKernelGGL(k_replay, dim3((nconn + RP_WG - 1u) / RP_WG), dim3(RP_WG), 0, st, (const Conn *)set->hdr,
+                     (const Entry *)set->ring, nconn, tb, wire, (uint64_t)wire_bytes, block_off, n, op_off, ops, cap,
+                     block_status, totals, dst_off, status, nlits, conn_blk_off, conn_blk, out_status, w.blk_count,
+                     w.blk_bytes, w.left, w.fresh, w.fref);
+  hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(SC_WG), 0, st, totals, (const uint32_t *)w.blk_count, w.blk_bytes, n,
+                     clamp32(nva_cap), clamp32(arena_cap), block_nv_off, out_totals);
+  if (cap)
+    hipLaunchKernelGGL(k_emit, dim3((cap + EM_WG - 1u) / EM_WG), dim3(EM_WG), 0, st, stores, totals, op_off, n, cap,
+                       (const FieldRef *)w.fref, (const uint32_t *)block_nv_off, (const uint32_t *)w.blk_bytes,
+                       (const uint32_t *)out_totals, nva, clamp32(nva_cap), arena, clamp32(arena_cap));
+  hipLaunchKernelGGL(k_commit, dim3(nconn), dim3(CM_WG), 0, st, stores, totals, (const uint32_t *)out_totals,
+                     (const Left *)w.left, (const Entry *)w.fresh, set->hdr, set->ring, set->store, tb);
+  return hdhost::hip_rv(hipGetLastError());
+}
+
+/* ---- the host twin: the same walk over host arrays, no GPU call ---- */
+
+void nghttp2_amd_hd_replay_host_init(nghttp2_amd_hd_dev_conn *hdr) {
+  if (hdr) hdreplay::conn_init(hdr);
+}
+
+int nghttp2_amd_hd_replay_host_change_table_size(nghttp2_amd_hd_dev_conn *hdr, const void *ring, uint32_t table_bytes,
+                                                 uint32_t value) {
+  if (!hdr || !ring || !table_bytes_ok(table_bytes)) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  return hdreplay::change_table_size(hdr, (const Entry *)ring, table_bytes, value);
+}
+
+int nghttp2_amd_hd_replay_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, uint8_t *store, uint32_t table_bytes,
+                               const uint8_t *wire, size_t wire_bytes, const uint32_t *block_off, uint32_t nblocks,
+                               const uint32_t *op_off, const nghttp2_amd_hd_op *ops, const int32_t *block_status,
+                               const uint8_t *dst, const uint32_t *dst_off, const int32_t *status, uint32_t nlits,
+                               nghttp2_amd_hd_nv *nva, size_t nva_cap, uint8_t *arena, size_t arena_cap,
+                               uint32_t *block_nv_off, int32_t *out_status, uint32_t *out_totals) {
+  const uint32_t n = nblocks;
+  if (n == 0) return 0;
+  if (!hdr || !ring_ || !store || !table_bytes_ok(table_bytes) || !wire || !ops || !block_off || !op_off || !block_status ||
+      (!nva && nva_cap) || (!arena && arena_cap) || !block_nv_off || !out_status || !out_totals ||
+      (nlits && (!dst || !dst_off || !status)) || hdr->count > table_bytes / hdreplay::kOverhead)
+    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  Entry *ring = (Entry *)ring_;
+  const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
+  std::vector<Entry> fresh(slots);
+  std::vector<FieldRef> fref(op_off[n] - op_off[0]);
+  const uint32_t cur = hdr->cur & 1u;
+  hdreplay::Table t;
+  hdreplay::table_open(&t, *hdr, ring, fresh.data(), table_bytes, cur * table_bytes);
+  const hdreplay::Lits lits = {dst_off, status, nlits};
+  uint64_t fields = 0, bytes = 0;
+  std::vector<uint64_t> base(n);
+  for (uint32_t b = 0; b < n; ++b) {
+    const uint32_t w0 = block_off[b], w1 = block_off[b + 1];
+    const bool first_is_size = w0 < w1 && w0 < wire_bytes && (wire[w0] & 0xE0u) == 0x20u;
+    FieldRef *out = fref.data() + (op_off[b] - op_off[0]);
+    const hdreplay::BlockResult r =
+        hdreplay::walk_block(&t, b, ops + op_off[b], op_off[b + 1] - op_off[b], block_status[b] >= 0, first_is_size,
+                             lits, &hdhost::kStaticPool, [out](uint32_t k, const FieldRef &fr) { out[k] = fr; });
+    out_status[b] = r.status;
+    block_nv_off[b] = (uint32_t)fields;
+    base[b] = bytes;
+    fields += r.fields;
+    bytes += r.bytes;
+  }
+  block_nv_off[n] = (uint32_t)fields;
+  const bool wide = ((fields | bytes) >> 32) != 0;
+  out_totals[0] = wide ? 0xFFFFFFFFu : (uint32_t)fields;
+  out_totals[1] = wide ? 0xFFFFFFFFu : (uint32_t)bytes;
+  out_totals[2] = (wide ? NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 : 0u) | (fields > nva_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_NVA : 0u) |
+                  (bytes > arena_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_ARENA : 0u);
+  out_totals[3] = 0u;
+  if (out_totals[2]) return 0;  // all or nothing: no field, and the table as it was
+  const uint8_t *stores[4] = {hdhost::kStaticPool.bytes, wire, dst, store};
+  auto bytes_of = [&](Ref r) { return stores[hdreplay::ref_src(r)] + r.off; };
+  for (const FieldRef &fr : fref) {
+    if (fr.block == hdreplay::kNoField) continue;
+    const uint32_t nl = hdreplay::ref_len(fr.name), vl = hdreplay::ref_len(fr.value);
+    const uint32_t at = (uint32_t)base[fr.block] + fr.before;
+    nghttp2_amd_hd_nv nv = {};
+    nv.block = fr.block;
+    nv.name_off = at;
+    nv.name_len = nl;
+    nv.value_off = at + nl + 1u;
+    nv.value_len = vl;
+    nv.flags = (uint8_t)fr.flags;
+    nva[block_nv_off[fr.block] + fr.ordinal] = nv;
+    if (nl) memcpy(arena + at, bytes_of(fr.name), nl);
+    arena[at + nl] = 0;
+    if (vl) memcpy(arena + nv.value_off, bytes_of(fr.value), vl);
+    arena[nv.value_off + vl] = 0;
+  }
+  // the commit: the live entries' bytes back to back into the other buffer
+  const uint32_t other = cur ^ 1u, count = t.nnew + t.nold, head = (t.h.head - t.nnew) & mask;
+  uint8_t *to = store + (size_t)other * table_bytes;
+  uint32_t at = 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const Entry e = hdreplay::table_get(t, i);
+    const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
+    if (nl) memcpy(to + at, bytes_of(e.name), nl);
+    if (vl) memcpy(to + at + nl, bytes_of(e.value), vl);
+    Entry d;
+    d.name = hdreplay::make_ref(hdreplay::SRC_TABLE, at, nl);
+    d.value = hdreplay::make_ref(hdreplay::SRC_TABLE, at + nl, vl);
+    ring[(head + i) & mask] = d;
+    at += nl + vl;
+  }
+  *hdr = t.h;
+  hdr->head = head;
+  hdr->count = count;
+  hdr->cur = other;
+  return 0;
+}
+
+}  // extern "C"

@@ -838,6 +838,322 @@ def inflate_blocks(inflaters, blocks, stream=None, nva_cap=None, arena_cap=None,
 
 
 # ---------------------------------------------------------------------------
+# Device-resident inflaters (nghttp2_amd_hd_dev_*, nghttp2_amd_hd_replay_host)
+# ---------------------------------------------------------------------------
+NGHTTP2_ERR_NOMEM = -901
+DEV_EXPECT_SIZE, DEV_BAD, DEV_MID_BLOCK = 0x1, 0x2, 0x4
+DEV_OVERFLOW_NVA, DEV_OVERFLOW_ARENA, DEV_OVERFLOW_U32 = 0x1, 0x2, 0x4
+DEV_CONN_DTYPE = np.dtype([(f, "<u4") for f in ("max", "settings_max", "min_max", "size", "count", "head",
+                                                "flags", "cur")])
+assert DEV_CONN_DTYPE.itemsize == 32
+
+
+def _replay_lib():
+    L = lib()
+    if not getattr(L, "_replay_bound", False):
+        vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
+        L.nghttp2_amd_hd_dev_inflaters_new.argtypes = [ctypes.POINTER(vp), u32, u32, vp]
+        L.nghttp2_amd_hd_dev_inflaters_del.argtypes = [vp]
+        L.nghttp2_amd_hd_dev_inflaters_del.restype = None
+        L.nghttp2_amd_hd_dev_inflaters_change_table_size.argtypes = [vp, vp, vp, vp, u32, vp]
+        L.nghttp2_amd_hd_dev_inflaters_read.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.nghttp2_amd_hd_dev_inflate_workspace_size.argtypes = [u32, u32, sz, u32]
+        L.nghttp2_amd_hd_dev_inflate_workspace_size.restype = sz
+        L.nghttp2_amd_hd_dev_inflate_blocks.argtypes = [vp, vp, sz, vp, u32, vp, vp, sz, vp, vp, vp, sz, vp, vp,
+                                                        u32, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
+        L.nghttp2_amd_hd_replay_host_init.argtypes = [vp]
+        L.nghttp2_amd_hd_replay_host_init.restype = None
+        L.nghttp2_amd_hd_replay_host_change_table_size.argtypes = [vp, vp, u32, u32]
+        L.nghttp2_amd_hd_replay_host.argtypes = [vp, vp, vp, u32, vp, sz, vp, u32, vp, vp, vp, vp, vp, vp, u32,
+                                                 vp, sz, vp, sz, vp, vp, vp]
+        L._replay_bound = True
+    return L
+
+
+def replay_fields(nva, arena, block_nv_off, out_status):
+    """A replay's results (host arrays, or the device tensors of a
+    ReplayedBlocks: synchronises) as inflate_blocks returns them:
+    (status[i], fields[i] = [(name, value, flags)])."""
+    def host(a):
+        return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    off = host(block_nv_off).view(np.uint32).tolist()
+    status = host(out_status).view(np.int32).tolist()
+    nv = host(nva).reshape(-1).view(np.uint8)[:_NV_DTYPE.itemsize * off[-1]].view(_NV_DTYPE)
+    raw = host(arena).tobytes()
+    flat = [(raw[no:no + nl], raw[vo:vo + vl], fl)
+            for no, nl, vo, vl, fl in zip(nv["name_off"].tolist(), nv["name_len"].tolist(),
+                                          nv["value_off"].tolist(), nv["value_len"].tolist(),
+                                          nv["flags"].tolist())]
+    return status, [flat[off[i]:off[i + 1]] for i in range(len(status))]
+
+
+def _conn_state(hdr, entries, raw):
+    e = entries[:4 * int(hdr["count"])].reshape(-1, 4).tolist()
+    return [(raw[a:a + b], raw[c:c + d]) for a, b, c, d in e]
+
+
+class HostReplayInflater:
+    """One connection of a DeviceInflaters set on the host
+    (nghttp2_amd_hd_replay_host; no GPU): the same header, ring and stores,
+    walked by the same code.  What the device results are compared with."""
+
+    def __init__(self, table_bytes=4096):
+        self.L = _replay_lib()
+        self.table_bytes = int(table_bytes)
+        self.hdr = np.zeros(1, DEV_CONN_DTYPE)
+        self.ring = np.zeros(self.table_bytes // 32 * 4, np.uint32)
+        self.store = np.zeros(2 * self.table_bytes, np.uint8)
+        self.L.nghttp2_amd_hd_replay_host_init(self.hdr.ctypes.data)
+
+    def change_table_size(self, value):
+        rv = self.L.nghttp2_amd_hd_replay_host_change_table_size(self.hdr.ctypes.data, self.ring.ctypes.data,
+                                                                 self.table_bytes, int(value))
+        if rv != NGHTTP2_ERR_INVALID_STATE:
+            _check(rv, "replay_host_change_table_size")
+        return rv
+
+    def replay(self, wire, block_off, op_off, ops, block_status, dst=None, dst_off=None, status=None,
+               nva_cap=None, arena_cap=None):
+        """The blocks wire[block_off[i]:block_off[i+1]] with the records
+        ops[op_off[i]:op_off[i+1]] (OP_DTYPE, offsets into wire) and parse
+        statuses block_status, in order on this connection; literal k is
+        dst[dst_off[k]:+status[k]].  Returns (out_totals, nva, arena,
+        block_nv_off, out_status) as numpy arrays; with an overflow bit in
+        out_totals[2] nothing was emitted and the table is as before."""
+        n = len(block_off) - 1
+        w = np.frombuffer(bytes(wire) + b"\0", np.uint8)
+        block_off = np.ascontiguousarray(block_off, np.uint32)
+        op_off = np.ascontiguousarray(op_off, np.uint32)
+        ops = np.ascontiguousarray(ops, OP_DTYPE) if len(ops) else np.zeros(1, OP_DTYPE)
+        block_status = np.ascontiguousarray(block_status, np.int32)
+        nlits = 0 if status is None else len(status)
+        if nlits:
+            dst = np.ascontiguousarray(dst, np.uint8) if len(dst) else np.zeros(1, np.uint8)
+            dst_off = np.ascontiguousarray(dst_off, np.uint32)
+            status = np.ascontiguousarray(status, np.int32)
+        nva_cap = max(1, len(ops)) if nva_cap is None else int(nva_cap)
+        if arena_cap is None:  # the exact need, from a run that emits nothing
+            r = self.replay(wire, block_off, op_off, ops, block_status, dst, dst_off, status, nva_cap, 0)
+            if not r[0][2] & DEV_OVERFLOW_ARENA:  # (no byte needed: that run was the call)
+                return r
+            arena_cap = int(r[0][1])
+        nva = np.zeros(max(1, nva_cap), _NV_DTYPE)
+        arena = np.zeros(max(1, arena_cap), np.uint8)
+        nv_off = np.zeros(n + 1, np.uint32)
+        out_status = np.zeros(max(1, n), np.int32)
+        totals = np.zeros(4, np.uint32)
+
+        def ptr(a):  # the decode's arrays are not read without literals
+            return a.ctypes.data if nlits else None
+        rv = self.L.nghttp2_amd_hd_replay_host(
+            self.hdr.ctypes.data, self.ring.ctypes.data, self.store.ctypes.data, self.table_bytes, w.ctypes.data,
+            len(w) - 1, block_off.ctypes.data, n, op_off.ctypes.data, ops.ctypes.data, block_status.ctypes.data,
+            ptr(dst), ptr(dst_off), ptr(status), nlits,
+            nva.ctypes.data, nva_cap, arena.ctypes.data, arena_cap, nv_off.ctypes.data, out_status.ctypes.data,
+            totals.ctypes.data)
+        _check(rv, "replay_host")
+        return totals, nva, arena[:arena_cap], nv_off, out_status[:n]
+
+    def table(self):
+        """[(name, value)] of the dynamic table, most recent first."""
+        h = self.hdr[0]
+        slots = self.table_bytes // 32
+        ring = self.ring.reshape(-1, 4)
+        raw = self.store[int(h["cur"]) * self.table_bytes:][:self.table_bytes].tobytes()
+        out = []
+        for i in range(int(h["count"])):
+            a, b, c, d = (int(x) for x in ring[(int(h["head"]) + i) % slots])
+            out.append((raw[a:a + (b & 0xFFFFFF)], raw[c:c + (d & 0xFFFFFF)]))
+        return out
+
+    def table_size(self):
+        return int(self.hdr[0]["size"])
+
+    def table_max(self):
+        return int(self.hdr[0]["max"])
+
+    def flags(self):
+        """(expect_size, bad, mid_block)"""
+        f = int(self.hdr[0]["flags"])
+        return bool(f & DEV_EXPECT_SIZE), bool(f & DEV_BAD), bool(f & DEV_MID_BLOCK)
+
+
+# What DeviceInflaters.inflate_parsed / .inflate return: device tensors.  nva
+# is uint8 [24 * nva_cap] (nghttp2_amd_hd_nv records), arena uint8, block_nv_off
+# int32[n+1] holding uint32, status int32[n], totals int32[4] = {fields, arena
+# bytes, DEV_OVERFLOW_* bits, 0}.  replay_fields(*r[:4]) gives the fields.
+ReplayedBlocks = collections.namedtuple("ReplayedBlocks", "nva arena block_nv_off status totals")
+
+
+class DeviceInflaters:
+    """nconn HPACK decoding contexts in device memory
+    (nghttp2_amd_hd_dev_inflaters): the end of the chain parse -> gather ->
+    decode_auto for wire that lies on the device.  table_bytes is the
+    capacity per connection (a power of two >= 4096): an insertion the HPACK
+    maximum admits and the store cannot hold ends its block with
+    NGHTTP2_ERR_NOMEM.  Calls on one set are ordered by their stream."""
+
+    def __init__(self, nconn, table_bytes=4096, device=None, stream=None):
+        import torch
+        self.torch = torch
+        self.device = torch.device(device if device is not None else "cuda")
+        self.L = _replay_lib()
+        self.nconn, self.table_bytes = int(nconn), int(table_bytes)
+        self._ws = None
+        p = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.L.nghttp2_amd_hd_dev_inflaters_new(ctypes.byref(p), self.nconn, self.table_bytes,
+                                                           _stream(stream)), "dev_inflaters_new")
+        self.p = p
+
+    def __del__(self):
+        if getattr(self, "p", None):
+            self.torch.cuda.synchronize(self.device)
+            self.L.nghttp2_amd_hd_dev_inflaters_del(self.p)
+            self.p = None
+
+    def _dev(self, a, dtype):
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype).view(np.int32)).to(self.device)
+
+    def change_table_size(self, conns, values, stream=None):
+        """nghttp2_hd_inflate_change_table_size for connection conns[i] with
+        values[i]; a connection appears at most once.  Returns the rv's as a
+        device int32 tensor (0 or NGHTTP2_ERR_INVALID_STATE)."""
+        conns = [int(c) for c in conns]
+        if len(set(conns)) != len(conns):
+            raise ValueError("change_table_size: a connection appears more than once")
+        if any(c < 0 or c >= self.nconn for c in conns):
+            raise ValueError("change_table_size: connection out of range")
+        n = len(conns)
+        rv = self.torch.zeros(max(1, n), dtype=self.torch.int32, device=self.device)
+        if n:
+            c = self._dev(conns, np.uint32)
+            v = self._dev([int(x) for x in values], np.uint32)
+            _check(self.L.nghttp2_amd_hd_dev_inflaters_change_table_size(self.p, _p(c), _p(v), _p(rv), n,
+                                                                         _stream(stream)),
+                   "dev_inflaters_change_table_size")
+        return rv[:n]
+
+    def _read(self, c, stream=None):
+        hdr = np.zeros(1, DEV_CONN_DTYPE)
+        ent = np.zeros(self.table_bytes // 32 * 4, np.uint32)
+        raw = np.zeros(self.table_bytes, np.uint8)
+        _check(self.L.nghttp2_amd_hd_dev_inflaters_read(self.p, int(c), hdr.ctypes.data, ent.ctypes.data,
+                                                        raw.ctypes.data, _stream(stream)), "dev_inflaters_read")
+        return hdr[0], ent, raw.tobytes()
+
+    def table(self, c, stream=None):
+        """[(name, value)] of connection c's dynamic table, most recent first
+        (synchronises the stream)."""
+        return _conn_state(*self._read(c, stream))
+
+    def table_size(self, c, stream=None):
+        return int(self._read(c, stream)[0]["size"])
+
+    def table_max(self, c, stream=None):
+        return int(self._read(c, stream)[0]["max"])
+
+    def state(self, c, stream=None):
+        """(table, size, max, (expect_size, bad, mid_block)) in one read."""
+        h, ent, raw = self._read(c, stream)
+        f = int(h["flags"])
+        return (_conn_state(h, ent, raw), int(h["size"]), int(h["max"]),
+                (bool(f & DEV_EXPECT_SIZE), bool(f & DEV_BAD), bool(f & DEV_MID_BLOCK)))
+
+    def csr(self, conn_of_block):
+        """conn_blk_off[nconn+1], conn_blk[n] (device int32 tensors) from the
+        connection of every block: a stable sort, so a connection's blocks
+        stay in batch order."""
+        conn = np.asarray(conn_of_block, np.int64)
+        if len(conn) and (conn.min() < 0 or conn.max() >= self.nconn):
+            raise ValueError("conn_of_block: connection out of range")
+        order = np.argsort(conn, kind="stable").astype(np.uint32)
+        off = np.zeros(self.nconn + 1, np.uint32)
+        np.cumsum(np.bincount(conn, minlength=self.nconn), out=off[1:])
+        return self._dev(off, np.uint32), self._dev(order if len(order) else [0], np.uint32)
+
+    def inflate_parsed(self, wire, block_off, parsed, dst, dst_off, status, conn_blk_off, conn_blk,
+                       nva_cap=None, arena_cap=None, stream=None):
+        """nghttp2_amd_hd_dev_inflate_blocks on tensors: the parse's results
+        (a ParsedBlocks), the decode's (dst, dst_off, status; None for a batch
+        without Huffman literals) and the CSR of csr().  nva_cap defaults to
+        the parse's ops_cap, which cannot overflow.  Nothing is read back:
+        returns a ReplayedBlocks."""
+        torch = self.torch
+        n = block_off.numel() - 1
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        ops_cap = parsed.ops.shape[0]
+        nva_cap = ops_cap if nva_cap is None else int(nva_cap)
+        arena_cap = 4 * parsed.wire_bytes + 4096 if arena_cap is None else int(arena_cap)
+        need = self.L.nghttp2_amd_hd_dev_inflate_workspace_size(self.nconn, self.table_bytes, ops_cap, n)
+        with torch.cuda.stream(s):
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            nva = torch.empty(max(1, nva_cap) * _NV_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+            arena = torch.empty(max(1, arena_cap), dtype=torch.uint8, device=self.device)
+            nv_off = torch.zeros(n + 1, dtype=torch.int32, device=self.device)
+            out_status = torch.empty(max(1, n), dtype=torch.int32, device=self.device)
+            totals = torch.zeros(4, dtype=torch.int32, device=self.device)
+            if wire.numel() == 0:
+                wire = torch.empty(16, dtype=torch.uint8, device=self.device)
+            nlits = 0 if dst is None else status.numel()
+            if dst is None:  # never read: the call is told there is no literal
+                dst = torch.empty(16, dtype=torch.uint8, device=self.device)
+                dst_off = status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        rv = self.L.nghttp2_amd_hd_dev_inflate_blocks(
+            self.p, _p(wire), parsed.wire_bytes, _p(block_off), n, _p(parsed.op_off), _p(parsed.ops), ops_cap,
+            _p(parsed.block_status), _p(parsed.totals), _p(dst), dst.numel(), _p(dst_off), _p(status), nlits,
+            _p(conn_blk_off), _p(conn_blk), _p(nva), nva_cap, _p(arena), arena_cap, _p(nv_off), _p(out_status),
+            _p(totals), _p(self._ws), self._ws.numel(), ctypes.c_void_p(s.cuda_stream))
+        _check(rv, "dev_inflate_blocks")
+        return ReplayedBlocks(nva, arena[:arena_cap], nv_off, out_status[:n], totals)
+
+    def inflate(self, codec, wire, block_off, conn_of_block, wire_bytes=None, nlits=None, enc_bytes=None,
+                arena_cap=None, stream=None, csr=None):
+        """parse -> gather -> decode_auto -> replay of a batch on the device:
+        block i is wire[block_off[i]:block_off[i+1]] and belongs to
+        connection conn_of_block[i] (a host sequence).  Returns a
+        ReplayedBlocks of device tensors.  Two things make the host wait for
+        the stream, and both can be avoided.  The CSR is built from
+        conn_of_block on the host and uploaded, which waits for the work
+        queued before it: pass csr=self.csr(conn_of_block), built ahead (then
+        conn_of_block is not read and may be None).  And the chain keeps one
+        host read, the decode's string count (the parse's totals[1], read with
+        totals[2]): pass nlits (and enc_bytes, else the wire's size bounds
+        it); a count below the batch's fails the fields of the literals past
+        it.  With csr, nlits and an arena_cap, calls queue on the stream with
+        no host synchronisation between them.  Without an arena_cap the call starts from four times the wire,
+        reads out_totals and repeats the replay with the reported need when
+        the arena was too small; with one, nothing is read and an overflow
+        is the caller's to see in totals[2]."""
+        torch = self.torch
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        off, blk = csr if csr is not None else self.csr(conn_of_block)
+        pb = codec.parse_blocks(wire, block_off, wire_bytes=wire_bytes, stream=s)
+        pool, lit_off = codec.gather_huffman_literals(wire, pb, stream=s)
+        if nlits is None:
+            with torch.cuda.stream(s):
+                t = pb.totals.cpu().numpy().view(np.uint32)
+            if t[3]:
+                raise RuntimeError("nghttp2_amd: the parse overflowed (totals[3] = %d)" % t[3])
+            nlits, enc_bytes = int(t[1]), int(t[2])
+        elif enc_bytes is None:
+            enc_bytes = pb.wire_bytes
+        dec = (None, None, None)
+        if nlits:
+            dec = codec.decode_auto(pool, lit_off[:nlits + 1], enc_bytes=enc_bytes, stream=s)
+        r = self.inflate_parsed(wire, block_off, pb, dec[0], dec[1], dec[2], off, blk, arena_cap=arena_cap,
+                                stream=s)
+        if arena_cap is None:
+            with torch.cuda.stream(s):
+                t = r.totals.cpu().numpy().view(np.uint32)
+            if t[2] & DEV_OVERFLOW_ARENA and not t[2] & DEV_OVERFLOW_U32:
+                r = self.inflate_parsed(wire, block_off, pb, dec[0], dec[1], dec[2], off, blk,
+                                        arena_cap=int(t[1]), stream=s)
+        return r
+
+
+# ---------------------------------------------------------------------------
 # Batched HPACK deflate front-end (nghttp2_amd_hd_deflate_*)
 # ---------------------------------------------------------------------------
 class _NvIn(ctypes.Structure):

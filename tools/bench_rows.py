@@ -927,6 +927,143 @@ def bench_parse(nconn=256, per_conn=8, fields=16, runs=5, steps=20):
                     "inflater's own trace of the same batch, medians of 5 calls per run"}
 
 
+def bench_dev_inflate(nconn=256, per_conn=8, fields=16, runs=5, steps=20):
+    """The device-resident chain parse + gather + decode_auto +
+    nghttp2_amd_hd_dev_inflate_blocks on the 2,048-block batch (resident
+    wire, the C calls on tensors allocated once, the decode's string count
+    known on the host) against nghttp2_amd_hd_inflate_blocks on the same
+    blocks, in one process, alternating call by call with fresh contexts
+    each run: each run times `steps` calls of the chain between HIP events
+    and as wall time around the calls and one stream synchronisation, and
+    `steps` host calls as wall time.  The row reports each run's medians and
+    the spread of those medians over the runs."""
+    import ctypes
+    import statistics
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    blocks, conns = make_blocks(nconn, per_conn, fields)
+    m = len(blocks)
+    wire = b"".join(blocks)
+    W = len(wire)
+    off = np.cumsum([0] + [len(b) for b in blocks]).astype(np.uint32)
+    dev = torch.device("cuda:0")
+    codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    L = hd._replay_lib()
+    tw = torch.from_numpy(np.frombuffer(bytearray(wire), np.uint8)).to(dev)
+    to = torch.from_numpy(off.view(np.int32)).to(dev)
+    # the batch's sizes, the results to hold the timed calls to, and the host call's own results
+    first = nghttp2_amd.DeviceInflaters(nconn, 4096)
+    r0 = first.inflate(codec, tw, to, conns)
+    want = hd.replay_fields(r0.nva, r0.arena, r0.block_nv_off, r0.status)
+    nfields, nbytes = (int(x) for x in r0.totals.cpu().numpy().view(np.uint32)[:2])
+    hs, hf = nghttp2_amd.inflate_blocks(_fresh_for(conns, nconn), blocks)
+    assert (hs, hf) == want
+    ops_cap, lits_cap, pool_cap, ws_bytes = hd.parse_blocks_bound(W, m)
+    i32, u8 = torch.int32, torch.uint8
+    ops = torch.empty((ops_cap, 8), dtype=i32, device=dev)
+    op_off, lit_base = torch.empty(m + 1, dtype=i32, device=dev), torch.empty(m + 1, dtype=i32, device=dev)
+    status, totals = torch.empty(m, dtype=i32, device=dev), torch.empty(4, dtype=i32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=u8, device=dev)
+    lit_off = torch.empty(lits_cap + 1, dtype=i32, device=dev)
+    pool = torch.empty(pool_cap, dtype=u8, device=dev)
+    st = hd._stream(None)
+    p = hd._p
+    L.nghttp2_amd_hd_parse_blocks_batch(p(tw), p(to), m, p(op_off), p(ops), ops_cap, p(status), p(lit_base), p(totals),
+                                        p(ws), ws_bytes, st)
+    tot = [int(x) for x in totals.cpu().numpy().view(np.uint32)]
+    T, E = tot[1], tot[2]
+    dst = torch.empty(codec.decode_bound(E, T), dtype=u8, device=dev)
+    dst_off, dstatus = torch.empty(T + 1, dtype=i32, device=dev), torch.empty(T, dtype=i32, device=dev)
+    nva = torch.empty(24 * ops_cap, dtype=u8, device=dev)
+    arena = torch.empty(nbytes, dtype=u8, device=dev)
+    nv_off, out_status = torch.empty(m + 1, dtype=i32, device=dev), torch.empty(m, dtype=i32, device=dev)
+    out_totals = torch.empty(4, dtype=i32, device=dev)
+    csr_off, csr_blk = first.csr(conns)
+    rws = torch.empty(L.nghttp2_amd_hd_dev_inflate_workspace_size(nconn, 4096, ops_cap, m), dtype=u8, device=dev)
+    cur = {}
+
+    def chain():
+        rv = L.nghttp2_amd_hd_parse_blocks_batch(p(tw), p(to), m, p(op_off), p(ops), ops_cap, p(status), p(lit_base),
+                                                 p(totals), p(ws), ws_bytes, st)
+        rv |= L.nghttp2_amd_hd_gather_literals_batch(p(tw), W, p(ops), ops_cap, p(totals), p(lit_off), lits_cap,
+                                                     p(pool), pool_cap, st)
+        rv |= L.nghttp2_amd_hd_huff_decode_batch_auto(p(pool), p(lit_off), T, E, p(dst), dst.numel(), p(dst_off),
+                                                      p(dstatus), None, None, st)
+        rv |= L.nghttp2_amd_hd_dev_inflate_blocks(
+            cur["set"].p, p(tw), W, p(to), m, p(op_off), p(ops), ops_cap, p(status), p(totals), p(dst), dst.numel(),
+            p(dst_off), p(dstatus), T, p(csr_off), p(csr_blk), p(nva), ops_cap, p(arena), nbytes, p(nv_off),
+            p(out_status), p(out_totals), p(rws), rws.numel(), st)
+        assert rv == 0
+
+    LI = hd._inflate_lib()
+    keep = [ctypes.create_string_buffer(b, len(b)) for b in blocks]
+    ptrs = (ctypes.c_void_p * m)(*[ctypes.cast(k, ctypes.c_void_p) for k in keep])
+    lens = (ctypes.c_size_t * m)(*[len(b) for b in blocks])
+    hnva_cap, harena_cap = W + 16, 8 * W + 4096
+    hnva = (hd._Nv * hnva_cap)()
+    harena = (ctypes.c_uint8 * harena_cap)()
+    stc = (ctypes.c_int32 * m)()
+    nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
+
+    def inflate():
+        t0 = time.perf_counter()
+        rv = LI.nghttp2_amd_hd_inflate_blocks(cur["ip"], m, ptrs, lens, hnva, hnva_cap, ctypes.byref(nv_used), harena,
+                                              harena_cap, ctypes.byref(ar_used), stc, st)
+        assert rv == 0
+        return (time.perf_counter() - t0) * 1e6
+
+    s = torch.cuda.current_stream()
+    per_run = []
+    for _ in range(runs):
+        cur["set"] = nghttp2_amd.DeviceInflaters(nconn, 4096)
+        cur["infs"] = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+        cur["ip"] = (ctypes.c_void_p * m)(*[cur["infs"][c].p.value for c in conns])
+        for _ in range(3):
+            chain()
+            inflate()
+        ev, host, wall = [], [], []
+        for _ in range(steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            chain()
+            b.record(s)
+            ev.append((a, b))
+            host.append(inflate())
+        torch.cuda.synchronize()
+        for _ in range(steps):
+            s.synchronize()
+            t0 = time.perf_counter()
+            chain()
+            s.synchronize()
+            wall.append((time.perf_counter() - t0) * 1e6)
+            inflate()
+        t = [a.elapsed_time(b) * 1e3 for a, b in ev]
+        per_run.append({"chain_us_best": round(min(t), 2), "chain_us_median": round(float(np.median(t)), 2),
+                        "chain_wall_us_median": round(statistics.median(wall), 1),
+                        "inflate_call_us_median": round(statistics.median(host), 1)})
+    # the timed calls' last results are the batch's
+    got = hd.replay_fields(nva, arena, nv_off, out_status)
+    assert got == want and out_totals.cpu().numpy().view(np.uint32).tolist() == [nfields, nbytes, 0, 0]
+    spread = {}
+    for k in [k for k in per_run[0] if k.endswith("_median")]:
+        v = [r[k] for r in per_run]
+        spread[k] = {"median": round(statistics.median(v), 1), "min": min(v), "max": max(v)}
+    return {"blocks": m, "connections": nconn, "wire_bytes": W, "ops": tot[0], "huffman_literals": T,
+            "huffman_bytes": E, "fields": nfields, "arena_bytes": nbytes, "runs": runs, "steps": steps,
+            "over_runs": spread, "per_run": per_run,
+            "note": "chain: parse + gather + decode_batch_auto + dev_inflate_blocks, the C calls on preallocated "
+                    "tensors with resident wire; HIP events around the calls (_us_*) and wall time around the "
+                    "calls and one stream synchronisation (_wall_us_median); inflate_call: "
+                    "nghttp2_amd_hd_inflate_blocks on the same blocks from host memory, wall time"}
+
+
+def _fresh_for(conns, nconn):
+    import nghttp2_amd
+    infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+    return [infs[c] for c in conns]
+
+
 if __name__ == "__main__":
     rows = sys.argv[1:] or ["emit", "emit3", "inflate", "names"]
     fns = {"emit": bench_emit, "emit3": lambda: bench_emit(cfg=3), "inflate": bench_inflate,
@@ -941,5 +1078,6 @@ if __name__ == "__main__":
            "http_facts": bench_http_facts,
            "inflate_http": bench_inflate_http,
            "parse": bench_parse,
+           "dev_inflate": bench_dev_inflate,
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
