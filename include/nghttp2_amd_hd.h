@@ -744,6 +744,11 @@ NGHTTP2_AMD_EXTERN size_t nghttp2_amd_hd_inflate_get_max_dynamic_table_size(nght
  * call, so concurrent calls are serialised whole, host passes included; the
  * engine keeps its per-block buffers across calls and releases the surplus
  * when a call is far smaller than an earlier one.
+ * A block is cut into its representations by the code that
+ * nghttp2_amd_hd_parse_block runs (csrc/hd_parse.h).  A block_lens[i] above
+ * UINT32_MAX is NGHTTP2_AMD_ERR_INVALID_ARGUMENT, as it is there, before any
+ * inflater changes: the offsets of nghttp2_amd_hd_nv are uint32, so such a
+ * block could not be answered.
  */
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks(nghttp2_amd_hd_inflater *const *inflaters,
                                   uint32_t nblocks, const uint8_t *const *blocks,
@@ -763,7 +768,8 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks(nghttp2_amd_hd_inflater *co
  * and one byte per literal more in the copy back), raw literals on the host
  * inside the replay, static-table entries once per process, dynamic-table
  * entries when they are inserted: an indexed field costs no byte scan.
- * nv_checks == NULL is nghttp2_amd_hd_inflate_blocks itself.
+ * nv_checks == NULL is nghttp2_amd_hd_inflate_blocks itself.  A
+ * block_lens[i] above UINT32_MAX is NGHTTP2_AMD_ERR_INVALID_ARGUMENT, as there.
  */
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_inflater *const *inflaters,
                                   uint32_t nblocks, const uint8_t *const *blocks,
@@ -790,7 +796,8 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_checked(nghttp2_amd_hd_infl
  * independent, either may be NULL: nv_tokens == NULL is
  * nghttp2_amd_hd_inflate_blocks_checked, both NULL is
  * nghttp2_amd_hd_inflate_blocks -- no token launch, no byte more in the
- * copies, no host lookup.
+ * copies, no host lookup.  A block_lens[i] above UINT32_MAX is
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT, as for nghttp2_amd_hd_inflate_blocks.
  */
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_inflater *const *inflaters,
                                   uint32_t nblocks, const uint8_t *const *blocks,
@@ -833,7 +840,8 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_fields(nghttp2_amd_hd_infla
  * and block_http may be NULL; block_modes and block_state are both needed
  * (else NGHTTP2_AMD_ERR_INVALID_ARGUMENT) unless all four are NULL, which is
  * nghttp2_amd_hd_inflate_blocks_fields itself: no launch, no byte more in
- * the copies, no host work.
+ * the copies, no host work.  A block_lens[i] above UINT32_MAX is
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT, as for nghttp2_amd_hd_inflate_blocks.
  */
 #define NGHTTP2_AMD_HTTP_NOT_EXAMINED 1
 NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflater *const *inflaters,

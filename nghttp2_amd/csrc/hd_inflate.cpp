@@ -4,9 +4,10 @@
 // many connections) per call and sends every Huffman literal of the batch
 // through ONE GPU decode (nghttp2_amd_hd_huff_decode_batch_auto), instead of
 // one nghttp2_hd_huff_decode per literal:
-//   pass 1  parse each block's representations and literal extents (the
-//           wire is self-delimiting: no table state needed), collecting the
-//           Huffman literals into one pinned pool;
+//   pass 1  cut each block into its representations (hd_parse.h's walk and
+//           record, the device path's: the wire is self-delimiting, no table
+//           state needed), collecting the Huffman literals into one pinned
+//           pool;
 //   GPU     H2D, batch decode, D2H (async on the caller's stream);
 //   pass 2  replay the blocks in batch order against each inflater's dynamic
 //           table -- index resolution, insertion with eviction, table size
@@ -31,6 +32,7 @@
 #include "hd_field_classes.h"
 #include "hd_host.h"
 #include "hd_http.h"
+#include "hd_parse.h"
 #include "hd_tokens.h"
 #include "host_threads.h"
 
@@ -38,7 +40,6 @@ namespace {
 
 using namespace hdhost;  // the static table, hip_ok, DevBuf / PinnedBuf
 const char *const kLayer = "inflate";  // (in hip_ok's messages)
-const uint32_t kMaxNv = 65536;         // NGHTTP2_HD_MAX_NV
 const uint32_t kDefaultTable = 4096;   // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
 
 // The dynamic table (lib/nghttp2_hd.c hd_ringbuf + nghttp2_hd_entry, restated
@@ -228,35 +229,14 @@ struct nghttp2_amd_hd_inflater {
 
 namespace {
 
-// decode_length (lib/nghttp2_hd.c:882-945) for a whole block: the prefix
-// integer at in[*pos] (the resumable decoder below, which must finish
-// inside the block: the block is complete, in_final); false on overflow or
-// truncation.
-bool read_int(const uint8_t *in, size_t len, size_t *pos, uint32_t prefix, uint32_t *out) {
-  if (*pos >= len) return false;
-  size_t shift = 0;
-  int fin = 0;
-  const ptrdiff_t n = nghttp2_amd_hd_decode_length(out, &shift, &fin, 0, 0, in + *pos, in + len, prefix);
-  if (n < 0 || !fin) return false;
-  *pos += (size_t)n;
-  return true;
-}
+using hdparse::Literal;  // a record's name or value string literal (hdparse::literal)
 
-// A string literal: raw bytes, or a Huffman literal decoded on the GPU.
-struct Lit {
-  const uint8_t *p;
-  uint32_t len;
-  int32_t huff;  // index into the batch's Huffman literals, or -1
-};
-// One representation of a block (parsed in pass 1).
-struct Op {
-  enum Kind : uint8_t { SIZE, INDEXED, LITERAL } kind;
-  bool index_required = false, no_index = false, new_name = false;
-  uint32_t value = 0;  // SIZE: the new size; INDEXED / indexed-name LITERAL: the index
-  Lit name{nullptr, 0, -1}, val{nullptr, 0, -1};
-};
+// One block of the batch: its representations (pass 1, hdparse::walk: offsets
+// are positions in the block, Huffman literals numbered within the block until
+// number_block adds the block's base) and the block's bytes.
 struct alignas(128) Block {  // (aligned as BlockOut)
-  std::vector<Op> ops;
+  std::vector<nghttp2_amd_hd_op> ops;  // (kept across calls: no allocation once grown)
+  const uint8_t *in = nullptr;         // the block's bytes, for the records' raw literals
   bool parse_ok = true;
   bool first_is_size = false;  // the block's first byte opens a table size update
   // the output bound's parts (pass 1): fields, bytes other than dynamic-table
@@ -267,6 +247,9 @@ struct alignas(128) Block {  // (aligned as BlockOut)
   // longest, they bound what a dynamic-table reference of the block emits
   uint64_t lit_name = 0, lit_val = 0;
 };
+// (the replay walks a block's records in place, two to a cache line; a block's
+// own state stays within the one line its alignment gives it)
+static_assert(sizeof(nghttp2_amd_hd_op) == 32 && sizeof(Block) == 128, "the replay is sensitive to the record's size");
 
 // One emitted field: its name\0value\0 run's place in the bytes it was written
 // to, and what of its annotations the caller may have asked for.
@@ -358,52 +341,6 @@ Engine &engine() {
   return e;
 }
 
-// Pass 1: representations and literal extents of one block
-// (lib/nghttp2_hd.c:1942-1985 opcode dispatch; string literal = H bit,
-// 7-bit-prefix length <= NGHTTP2_HD_MAX_NV, bytes).
-bool parse_block(const uint8_t *in, size_t len, Block &b) {
-  size_t pos = 0;
-  auto read_lit = [&](Lit &l) {
-    if (pos >= len) return false;
-    const bool h = in[pos] & 0x80u;
-    uint32_t n;
-    if (!read_int(in, len, &pos, 7, &n) || n > kMaxNv || len - pos < n) return false;
-    l.p = in + pos;
-    l.len = n;
-    l.huff = h ? 0 : -1;
-    pos += n;
-    return true;
-  };
-  b.ops.clear();  // (kept across calls: no allocation once grown)
-  b.first_is_size = len > 0 && (in[0] & 0xE0u) == 0x20u;
-  b.ops.reserve(len / 4 + 1);
-  while (pos < len) {
-    Op op;
-    const uint8_t c = in[pos];
-    if ((c & 0xE0u) == 0x20u) {  // dynamic table size update
-      op.kind = Op::SIZE;
-      if (!read_int(in, len, &pos, 5, &op.value)) return false;
-    } else if (c & 0x80u) {  // indexed
-      op.kind = Op::INDEXED;
-      if (!read_int(in, len, &pos, 7, &op.value)) return false;
-    } else {
-      op.kind = Op::LITERAL;
-      op.index_required = (c & 0x40u) != 0;
-      op.no_index = (c & 0xF0u) == 0x10u;
-      if (c == 0x40u || c == 0 || c == 0x10u) {
-        op.new_name = true;
-        ++pos;
-        if (!read_lit(op.name)) return false;
-      } else if (!read_int(in, len, &pos, op.index_required ? 6 : 4, &op.value)) {
-        return false;
-      }
-      if (!read_lit(op.val)) return false;
-    }
-    b.ops.push_back(op);
-  }
-  return true;
-}
-
 // Where pass 2 finds a literal's bytes: the wire, or the decoded pool.
 struct LitSrc {
   const uint8_t *dec;
@@ -413,35 +350,36 @@ struct LitSrc {
   const int32_t *tok;  // a tokened call: the decoded literals' tokens (the GPU's)
   const uint32_t *fct;  // an _http call: the decoded literals' HTTP facts and numbers (the GPU's)
   const int64_t *num;
-  // false: -523 (bad padding or EOS, hd_inflate_read_huff :1740-1750)
-  bool get(const Lit &l, const char **p, size_t *n) const {
-    if (l.huff < 0) {
-      *p = (const char *)l.p;
+  // literal l of a block whose bytes are at in; false: -523 (bad padding or
+  // EOS, hd_inflate_read_huff :1740-1750)
+  bool get(const uint8_t *in, const Literal &l, const char **p, size_t *n) const {
+    if (!l.huff) {
+      *p = (const char *)in + l.off;
       *n = l.len;
       return true;
     }
-    const int32_t s = st[l.huff];
+    const int32_t s = st[l.lit];
     if (s < 0) return false;
-    *p = (const char *)dec + slot[l.huff];
+    *p = (const char *)dec + slot[l.lit];
     *n = (size_t)s;
     return true;
   }
   // what w asks for of a field whose value literal, and name literal unless
   // the name is an entry's (nullptr), get() returned: a raw literal is scanned
   // here (on the replay's thread), a Huffman one was scanned behind its decode
-  Ann ann(const Lit *name, const Lit &val, Want w) const {
+  Ann ann(const uint8_t *in, const Literal *name, const Literal &val, Want w) const {
     Ann a;
-    if (name && name->huff < 0) {
-      a.fill_name(name->p, name->len, w);
+    if (name && !name->huff) {
+      a.fill_name(in + name->off, name->len, w);
     } else if (name) {
-      if (w.checks) a.cn = chk[name->huff];
-      if (w.tokens) a.tk = (int8_t)tok[name->huff];
+      if (w.checks) a.cn = chk[name->lit];
+      if (w.tokens) a.tk = (int8_t)tok[name->lit];
     }
-    if (val.huff < 0) {
-      a.fill_value(val.p, val.len, w);
+    if (!val.huff) {
+      a.fill_value(in + val.off, val.len, w);
     } else {
-      if (w.checks) a.cv = chk[val.huff];
-      if (w.http) a.vf = fct[val.huff], a.vn = num[val.huff];
+      if (w.checks) a.cv = chk[val.lit];
+      if (w.http) a.vf = fct[val.lit], a.vn = num[val.lit];
     }
     return a;
   }
@@ -547,12 +485,12 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
   bool ok = !inf->bad;
   bool head = true;  // size updates only at the head of a block
   for (size_t k = 0; ok && k < b.ops.size(); ++k) {
-    const Op &op = b.ops[k];
-    if (inf->expect_size && op.kind != Op::SIZE) {
+    const nghttp2_amd_hd_op &op = b.ops[k];
+    if (inf->expect_size && op.kind != NGHTTP2_AMD_HD_OP_SIZE) {
       ok = false;
       break;
     }
-    if (op.kind == Op::SIZE) {
+    if (op.kind == NGHTTP2_AMD_HD_OP_SIZE) {
       if (!head || op.value > (inf->min_max < inf->settings_max ? inf->min_max : inf->settings_max)) {
         ok = false;
         break;
@@ -566,7 +504,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     head = false;
     const char *n, *v;
     size_t nl, vl;
-    if (op.kind == Op::INDEXED) {  // hd_inflate_commit_indexed
+    if (op.kind == NGHTTP2_AMD_HD_OP_INDEXED) {  // hd_inflate_commit_indexed
       if (op.value == 0 || op.value > inf->max_index()) {
         ok = false;
         break;
@@ -577,9 +515,11 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       out.emit(n, nl, v, vl, 0, a, http ? http->step(n, nl, vl, a) : 0);
       continue;
     }
+    const bool new_name = (op.flags & NGHTTP2_AMD_HD_OP_NEW_NAME) != 0;
+    const Literal name = hdparse::literal(op, 0), val = hdparse::literal(op, 1);
     const Ann *name_ann = nullptr;  // an indexed name's
-    if (op.new_name) {  // hd_inflate_commit_newname
-      if (!ls.get(op.name, &n, &nl)) {
+    if (new_name) {  // hd_inflate_commit_newname
+      if (!ls.get(b.in, name, &n, &nl)) {
         ok = false;
         break;
       }
@@ -593,15 +533,15 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       inf->entry(op.value - 1, &n, &nl, &v0, &vl0);
       if (want.any()) name_ann = &inf->entry_ann(op.value - 1, want);
     }
-    if (!ls.get(op.val, &v, &vl)) {
+    if (!ls.get(b.in, val, &v, &vl)) {
       ok = false;
       break;
     }
-    Ann a = ls.ann(op.new_name ? &op.name : nullptr, op.val, want);
+    Ann a = ls.ann(b.in, new_name ? &name : nullptr, val, want);
     if (name_ann) a.cn = name_ann->cn, a.tk = name_ann->tk;
-    const uint8_t flags = op.no_index ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
+    const uint8_t flags = (op.flags & NGHTTP2_AMD_HD_OP_NO_INDEX) ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
     out.emit(n, nl, v, vl, flags, a, http ? http->step(n, nl, vl, a) : 0);
-    if (op.index_required)  // the table copies the field just emitted
+    if (op.flags & NGHTTP2_AMD_HD_OP_INDEX_REQUIRED)  // the table copies the field just emitted
       inf->add(out.last_name(), nl, out.last_value(), vl, a);
   }
   // truncated or malformed wire after the parsed representations; and a
@@ -651,8 +591,8 @@ struct Dest {
 // dynamic one counted (dyn_ref_bound bounds it at replay).
 void bound_block(Block &b) {
   b.nv = b.ar = b.ndyn = b.lit_name = b.lit_val = 0;
-  auto lit_len = [](const Lit &l) -> uint64_t {
-    return l.huff < 0 ? (uint64_t)l.len : (uint64_t)l.len * 8u / 5u + 1u;
+  auto lit_len = [](const Literal &l) -> uint64_t {
+    return l.huff ? (uint64_t)l.len * 8u / 5u + 1u : (uint64_t)l.len;
   };
   auto ref = [&](uint32_t idx, bool name_only) {
     if (idx >= 1 && idx <= kStaticLen)
@@ -660,27 +600,32 @@ void bound_block(Block &b) {
     else
       ++b.ndyn;
   };
-  for (const Op &op : b.ops) {
-    if (op.kind == Op::SIZE) continue;
+  for (const nghttp2_amd_hd_op &op : b.ops) {
+    if (op.kind == NGHTTP2_AMD_HD_OP_SIZE) continue;
     ++b.nv;
     b.ar += 2u;
-    if (op.kind == Op::INDEXED) {
+    if (op.kind == NGHTTP2_AMD_HD_OP_INDEXED) {
       ref(op.value, false);
     } else {
-      if (op.new_name) {
-        b.ar += lit_len(op.name);
-        b.lit_name = std::max(b.lit_name, lit_len(op.name));
+      if (op.flags & NGHTTP2_AMD_HD_OP_NEW_NAME) {
+        const uint64_t n = lit_len(hdparse::literal(op, 0));
+        b.ar += n;
+        b.lit_name = std::max(b.lit_name, n);
       } else {
         ref(op.value, true);
       }
-      b.ar += lit_len(op.val);
-      b.lit_val = std::max(b.lit_val, lit_len(op.val));
+      const uint64_t v = lit_len(hdparse::literal(op, 1));
+      b.ar += v;
+      b.lit_val = std::max(b.lit_val, v);
     }
   }
 }
 
-// "parse blocks" -- pass 1: every block parsed and bounded, its Huffman
-// literals counted (stateless: one task per block).  The engine's per-block
+// "parse blocks" -- pass 1: every block cut into its representations by
+// hdparse::walk (lib/nghttp2_hd.c:1942-1985 opcode dispatch, string literals,
+// the truncation rule: stated there, once) and bounded; the walk's counts are
+// the block's Huffman literals and their bytes (stateless: one task per block,
+// so the literals are numbered within the block).  The engine's per-block
 // buffers are kept across calls, so a warm call allocates nothing here; a call
 // far below an earlier large batch releases the surplus (a high-water mark of 2x +
 // 4096 blocks), so one large batch does not pin its footprint for the process's life.
@@ -699,37 +644,36 @@ void parse_blocks(Engine &E, uint32_t nblocks, const uint8_t *const *blocks, con
     // a malformed block keeps the representations before the error: the
     // reference emits those fields before it fails
     Block &b = E.bl[i];
-    b.parse_ok = parse_block(blocks[i], block_lens[i], b);
-    uint32_t c = 0;
-    uint64_t by = 0;
-    for (const Op &op : b.ops)
-      if (op.kind == Op::LITERAL) {
-        if (op.name.huff == 0) ++c, by += op.name.len;
-        if (op.val.huff == 0) ++c, by += op.val.len;
-      }
-    E.nhuff[i + 1] = c;
-    E.hbytes[i + 1] = by;
+    const uint32_t len = (uint32_t)block_lens[i];  // (the entry point refuses a longer block)
+    b.in = blocks[i];
+    b.first_is_size = hdparse::first_is_size(b.in, len);
+    b.ops.clear();
+    b.ops.reserve(len / 4 + 1);
+    const hdparse::Counts c =
+        hdparse::walk(b.in, 0u, len, 0u, [&b](uint32_t, const nghttp2_amd_hd_op &op) { b.ops.push_back(op); });
+    b.parse_ok = c.ok;
+    E.nhuff[i + 1] = c.lits;
+    E.hbytes[i + 1] = c.lit_bytes;
     bound_block(b);
   });
 }
 
-// "number+copy": each block numbers its Huffman literals and copies their bytes into the
-// pinned input pool, in one parallel pass (round 5; before: numbering, then a separate gather).
+// "number+copy": each block gives its Huffman literals their numbers in the batch (pass 1's
+// block-local number plus k0, the Huffman literals of the blocks before: the walk's wire order,
+// a name before its value) and copies their bytes into the pinned input pool from o on, in one
+// parallel pass (round 5; before: numbering, then a separate gather).
 // (by-value arguments: the loop reads nothing that may share a line with parallel_for's counter)
-void number_block(Block &b, uint32_t k, uint32_t o, uint8_t *hp, uint32_t *hoff) {
-  for (Op &op : b.ops) {
-    if (op.kind != Op::LITERAL) continue;
-    if (op.name.huff == 0) {
-      op.name.huff = (int32_t)k;
-      memcpy(hp + o, op.name.p, op.name.len);
-      o += op.name.len;
-      hoff[++k] = o;
-    }
-    if (op.val.huff == 0) {
-      op.val.huff = (int32_t)k;
-      memcpy(hp + o, op.val.p, op.val.len);
-      o += op.val.len;
-      hoff[++k] = o;
+void number_block(Block &b, uint32_t k0, uint32_t o, uint8_t *hp, uint32_t *hoff) {
+  for (nghttp2_amd_hd_op &op : b.ops) {
+    if (op.kind != NGHTTP2_AMD_HD_OP_LITERAL) continue;
+    for (int which = 0; which < 2; ++which) {
+      const Literal l = hdparse::literal(op, which);
+      if (!l.huff) continue;
+      const uint32_t k = k0 + (uint32_t)l.lit;
+      (which ? op.value_lit : op.name_lit) = (int32_t)k;
+      memcpy(hp + o, b.in + l.off, l.len);
+      o += l.len;
+      hoff[k + 1] = o;
     }
   }
 }
@@ -1209,7 +1153,8 @@ int nghttp2_amd_hd_inflate_blocks_http(nghttp2_amd_hd_inflater *const *inflaters
   if (!inflaters || !blocks || !block_lens || !block_status || !nva_used || !arena_used)
     return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < nblocks; ++i)
-    if (!inflaters[i] || (!blocks[i] && block_lens[i])) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+    if (!inflaters[i] || (!blocks[i] && block_lens[i]) || block_lens[i] > UINT32_MAX)
+      return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   // an _http call: the modes and the states are its input, so both are needed
   const bool http = block_modes || block_state || nv_verdicts || block_http;
   if (http && (!block_modes || !block_state)) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;

@@ -16,10 +16,12 @@
 // statements whether the sink stores the record or drops it, so a count pass
 // and a write pass over the same bytes cannot disagree.
 //
-// Shared by the host function (nghttp2_amd_hd_parse_block) and the GPU kernels
-// (k_parse_blocks, one lane per block).  Plain C++17, no HIP: included by .cpp
-// and .hip sources alike.  No table, no array: on the device the walk keeps
-// its state in registers.
+// Shared by the host function (nghttp2_amd_hd_parse_block), pass 1 of the host
+// inflater (hd_inflate.cpp: parse_blocks) and the GPU kernels (k_parse_blocks,
+// one lane per block); both replays (hd_replay.h: walk_block, hd_inflate.cpp:
+// replay_block) read the record's string literals through literal() below.
+// Plain C++17, no HIP: included by .cpp and .hip sources alike.  No table, no
+// array: on the device the walk keeps its state in registers.
 #ifndef NGHTTP2_AMD_HD_PARSE_H
 #define NGHTTP2_AMD_HD_PARSE_H
 
@@ -46,6 +48,11 @@ constexpr uint32_t kMaxNv = 65536;  // NGHTTP2_HD_MAX_NV
 // integer the block end cuts off.  The groups that can pass sit at shifts 0,
 // 7, .. 28, so an integer is at most six bytes and the loop at most five
 // rounds.  On success *pos is past the integer.
+// Every parser of a whole block reads its integers here, the host inflater
+// included.  nghttp2_amd_hd_decode_length (hd_inflate.cpp) is the other
+// statement of the integer: public, and resumable across input chunks, which
+// a walk on the device has no use for.  tests/test_parse_blocks.py
+// (test_read_int_agrees_with_decode_length) holds the two to each other.
 HDPARSE_FN bool read_int(const uint8_t *in, uint32_t len, uint32_t *pos, uint32_t prefix, uint32_t *out) {
   uint32_t p = *pos;
   if (p >= len) return false;
@@ -87,6 +94,27 @@ HDPARSE_FN bool read_lit(const uint8_t *in, uint32_t len, uint32_t *pos, uint32_
   return true;
 }
 
+// Byte b0 opens a dynamic table size update (001xxxxx).
+HDPARSE_FN bool is_size_update(uint32_t b0) { return (b0 & 0xE0u) == 0x20u; }
+// The first byte of the block in[0, len) opens one.  Which state a failed
+// block leaves its inflater in depends on it (the replays' first_is_size).
+HDPARSE_FN bool first_is_size(const uint8_t *in, uint32_t len) { return len > 0u && is_size_update(in[0]); }
+
+// A record's name (which = 0) or value (which = 1) string literal: where its
+// bytes are and how many, whether they are Huffman-coded, and then its number
+// among the Huffman literals (else -1).  The one decoding of the record's
+// flag bits and literal fields; without NEW_NAME a LITERAL's name is {0, 0,
+// false, -1}.
+struct Literal {
+  uint32_t off, len;
+  bool huff;
+  int32_t lit;
+};
+HDPARSE_FN Literal literal(const nghttp2_amd_hd_op &op, int which) {
+  if (which) return Literal{op.value_off, op.value_len, (op.flags & NGHTTP2_AMD_HD_OP_VALUE_HUFF) != 0, op.value_lit};
+  return Literal{op.name_off, op.name_len, (op.flags & NGHTTP2_AMD_HD_OP_NAME_HUFF) != 0, op.name_lit};
+}
+
 // What a block holds: its completed representations, the Huffman literals
 // among their string literals and those literals' encoded bytes; ok is false
 // when the bytes after the last completed representation are no
@@ -119,7 +147,7 @@ HDPARSE_FN Counts walk(const uint8_t *in, uint32_t base, uint32_t len, uint32_t 
     op.name_lit = op.value_lit = -1;
     const uint32_t b0 = in[pos];
     uint32_t lits = 0, lit_bytes = 0;
-    if ((b0 & 0xE0u) == 0x20u) {  // dynamic table size update
+    if (is_size_update(b0)) {  // dynamic table size update
       op.kind = NGHTTP2_AMD_HD_OP_SIZE;
       if (!read_int(in, len, &pos, 5, &op.value)) break;
     } else if (b0 & 0x80u) {  // indexed

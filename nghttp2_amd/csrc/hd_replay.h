@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_parse.h"
 #include "hd_static.h"
 
 #if defined(__HIPCC__)
@@ -171,12 +172,12 @@ struct Lits {
 };
 // A record's name (which = 0) or value literal; false when its decode failed.
 HDREPLAY_FN bool literal_ref(const nghttp2_amd_hd_op &op, int which, const Lits &lits, Ref *out) {
-  const bool huff = (op.flags & (which ? NGHTTP2_AMD_HD_OP_VALUE_HUFF : NGHTTP2_AMD_HD_OP_NAME_HUFF)) != 0;
-  if (!huff) {
-    *out = make_ref(SRC_WIRE, which ? op.value_off : op.name_off, which ? op.value_len : op.name_len);
+  const hdparse::Literal l = hdparse::literal(op, which);
+  if (!l.huff) {
+    *out = make_ref(SRC_WIRE, l.off, l.len);
     return true;
   }
-  const uint32_t k = (uint32_t)(which ? op.value_lit : op.name_lit);
+  const uint32_t k = (uint32_t)l.lit;
   if (k >= lits.nlits) return false;
   const int32_t st = lits.status[k];
   if (st < 0 || (uint32_t)st > 0xFFFFFFu) return false;

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(RP_WG) void k_replay(
     if (b >= n) continue;
     const uint32_t r0 = min(op_off[b], nops), r1 = min(op_off[b + 1], nops);
     const uint32_t w0 = block_off[b], w1 = block_off[b + 1];
-    const bool first_is_size = w0 < w1 && w0 < wire_bytes && (wire[w0] & 0xE0u) == 0x20u;
+    const bool first_is_size = w0 < w1 && w0 < wire_bytes && hdparse::first_is_size(wire + w0, w1 - w0);
     const hdreplay::BlockResult r =
         hdreplay::walk_block(&t, b, ops + r0, r1 > r0 ? r1 - r0 : 0u, block_status[b] >= 0, first_is_size, lits,
                              &d_static, FrefStore{fref, r0, ops_cap});
@@ -511,7 +511,7 @@ int nghttp2_amd_hd_replay_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, uint8_
   std::vector<uint64_t> base(n);
   for (uint32_t b = 0; b < n; ++b) {
     const uint32_t w0 = block_off[b], w1 = block_off[b + 1];
-    const bool first_is_size = w0 < w1 && w0 < wire_bytes && (wire[w0] & 0xE0u) == 0x20u;
+    const bool first_is_size = w0 < w1 && w0 < wire_bytes && hdparse::first_is_size(wire + w0, w1 - w0);
     FieldRef *out = fref.data() + (op_off[b] - op_off[0]);
     const hdreplay::BlockResult r =
         hdreplay::walk_block(&t, b, ops + op_off[b], op_off[b + 1] - op_off[b], block_status[b] >= 0, first_is_size,

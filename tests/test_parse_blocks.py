@@ -119,6 +119,71 @@ def test_numbering_within_a_block():
     assert P.parse(blk, base=7, lit0=5)[1][3][8] == 8
 
 
+# prefix width -> (opcode bits, what completes the representation behind the
+# integer): indexed, size update, and a literal with an indexed name (with and
+# without indexing) followed by an empty raw value literal
+INT_FORMS = {7: (0x80, b""), 5: (0x20, b""), 6: (0x40, b"\x00"), 4: (0x00, b"\x00")}
+
+
+def _int_encodings(v, prefix, first):
+    """v under `first`'s bits: the shortest form and, of a value with
+    continuation groups, the forms padded with zero groups to runs of five and
+    of six groups."""
+    short = P.enc_int(v, prefix, first)
+    out = [short]
+    groups = len(short) - 1
+    for run in (5, 6):
+        if 0 < groups < run:
+            out.append(short[:-1] + bytes([short[-1] | 0x80]) + b"\x80" * (run - groups - 1) + b"\x00")
+    return out
+
+
+def test_read_int_agrees_with_decode_length():
+    """The two statements of the prefix integer, hdparse::read_int (every block
+    parser's, the inflater's included) and the public resumable
+    nghttp2_amd_hd_decode_length: a one-representation block is accepted
+    exactly when decode_length over the integer's bytes ends (fin) without an
+    error, and then with the same value and the same number of bytes consumed.
+    Every encoding is also cut after every byte; a cut one is a block that ends
+    inside its integer (what completes the representation follows a whole
+    encoding only).
+    A literal's name index of 0 is no integer: 0x40 / 0x00 open a literal with
+    a new name, so that cell of the grid asserts that instead."""
+    n = accepted_n = 0
+    for prefix, (first, tail) in INT_FORMS.items():
+        mask = (1 << prefix) - 1
+        values = [0, mask - 1, mask, mask + 1, mask + 127, mask + 128, 1 << 14, 1 << 21, 1 << 28, P.U32 - mask,
+                  P.U32, P.U32 + 1, mask + (1 << 35)]  # (the last: six groups, none of them padding)
+        for v in values:
+            if v == 0 and tail:
+                rv, ops = hd.parse_block(bytes([first]) + b"\x00" + tail)
+                assert rv == 0 and len(ops) == 1 and ops[0]["flags"] & hd.OP_NEW_NAME and ops[0]["value"] == 0
+                assert hd.parse_block(bytes([first]) + tail)[0] == hd.NGHTTP2_ERR_HEADER_COMP
+                continue
+            encs = _int_encodings(v, prefix, first)
+            assert sorted({len(e) - 1 for e in encs} - {len(encs[0]) - 1}) == \
+                [r for r in (5, 6) if 0 < len(encs[0]) - 1 < r]
+            for enc in encs:
+                for k in range(1, len(enc) + 1):
+                    cut = enc[:k]
+                    rv, value, _, fin = hd.decode_length(cut, prefix)
+                    block = cut + tail if k == len(enc) else cut
+                    prv, ops = hd.parse_block(block)
+                    assert prv in (0, hd.NGHTTP2_ERR_HEADER_COMP)
+                    assert (prv == 0) == (rv >= 0 and bool(fin)), (prefix, v, enc.hex(), k)
+                    n += 1
+                    if prv:
+                        assert len(ops) == 0
+                        continue
+                    accepted_n += 1
+                    assert len(ops) == 1 and int(ops[0]["value"]) == value == v, (prefix, v, enc.hex())
+                    # (a literal's value bytes start one length byte behind the integer)
+                    consumed = int(ops[0]["value_off"]) - 1 if tail else len(block)
+                    assert consumed == rv == len(enc), (prefix, v, enc.hex())
+    # (accepted: at least the shortest form of the 11 values within uint32 at four widths, less the two 0 cells)
+    assert n > 500 and accepted_n > 42
+
+
 INFLATE_CONNS = R.connections(None, "i")
 
 
