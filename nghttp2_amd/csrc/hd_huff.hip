@@ -552,16 +552,39 @@ __global__ __launch_bounds__(1024) void k_tile_prefix64(const uint32_t *__restri
 // FR: + the wave's literal prefixes and pads (64 x (6 x 8 + 7) bits)
 #define EC_RW_F (EC_RW + 112u)
 
-// OR the MSB-aligned bits {hi, lo} into the image at bit b
+// OR the MSB-aligned bits {hi, lo} into the image at bit b.  The position is
+// taken as a bit address in LDS, ba = 8 * (the image's byte address) + b, so
+// a lane that places several runs one after the other carries one sum and
+// pays a shift and a mask per run for the word's address (the image's base
+// added to b >> 5 every time was a third instruction); the shifts take the
+// bit offset from ba's low five bits as they are.
+__device__ __forceinline__ uint32_t ec_bit_addr(lds_u32 *img, uint32_t b) {
+  return 8u * (uint32_t)(uintptr_t)img + b;
+}
+__device__ __forceinline__ void ec_or3_at(uint32_t ba, uint32_t hi, uint32_t lo) {
+  lds_u32 *q = (lds_u32 *)(uintptr_t)((ba >> 3) & ~3u);
+  const uint32_t o = ba & 31u;
+  atomicOr((uint32_t *)&q[0], hi >> o);
+  atomicOr((uint32_t *)&q[1], __builtin_amdgcn_alignbit(hi, lo, o));
+  atomicOr((uint32_t *)&q[2], __builtin_amdgcn_alignbit(lo, 0u, o));  // (0 when o = 0)
+}
 __device__ __forceinline__ void ec_or3(lds_u32 *img, uint32_t b, uint32_t hi, uint32_t lo,
                                        uint32_t rw = 0xFFFFFFFFu) {
   HD_CHECK((b >> 5) + 2u < rw, 0x101u);
   (void)rw;
-  const uint32_t o = b & 31u;
-  lds_u32 *q = img + (b >> 5);
-  atomicOr((uint32_t *)&q[0], hi >> o);
-  atomicOr((uint32_t *)&q[1], __builtin_amdgcn_alignbit(hi, lo, o));
-  atomicOr((uint32_t *)&q[2], __builtin_amdgcn_alignbit(lo, 0u, o));  // (0 when o = 0)
+  ec_or3_at(ec_bit_addr(img, b), hi, lo);
+}
+
+// 8 * (the low byte of w), a codeT entry's byte offset, in one instruction:
+// the shift with a byte-select operand.  (The compiler forms the offsets of
+// a dword's bytes 1..3 this way from a shift and a mask, but keeps byte 0's
+// (w << 3) & 0x7F8 as two.)
+__device__ __forceinline__ uint32_t ec_byte0_x8(uint32_t w) {
+  uint32_t r;
+  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
+      : "=v"(r)
+      : "v"(3u), "v"(w));
+  return r;
 }
 
 // FR: emit_string (lib/nghttp2_hd.c:1001-1044) fused into the pack -- every
@@ -595,7 +618,13 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
   __shared__ uint32_t o_sh[WG + 1];
   __shared__ uint32_t red[2 * (WG / 64)];
   __shared__ uint8_t lenT1[ONE ? 256 : 1];
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  // (the pack: the wave's number as a scalar.  threadIdx.x >> 6 is a vector
+  // value to the compiler, and with it the wave's strings, its chunk range,
+  // the round's bit position, word bounds and store base were all vector
+  // registers: the round loop ran under an exec mask and formed every store
+  // address with 64-bit vector adds)
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = !FR ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
   // every load of the prologue is issued before any is used, so a tile's
   // start costs one memory latency (round 5: the staging, the offsets, the
   // tile sums and the tile's own sum waited in turn)
@@ -764,10 +793,15 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
     wave_lds_sync();
     const uint32_t p0 = base + 16u * lane;
     const bool act = p0 < Z;  // (lanes past the wave's last chunk: nothing)
+    // (the pack: this round's chunk, and the last round's stores, waited for
+    // here, before the next chunk's load is issued.  The wait falls here
+    // anyway; left to the compiler it can land behind that load, which sits
+    // in a branch, and then waits for it as well: no chunk in flight)
+    if (!FR) wait_vmcnt0();
     const uint32_t wd[4] = {wn.x, wn.y, wn.z, wn.w};
     wn = make_uint4(0, 0, 0, 0);
     if (cb + 64u + lane < c_end) wn = *reinterpret_cast<const uint4 *>(src + p0 + 1024u);
-#define EC_B8(j) (((j) & 3) ? (wd[(j) >> 2] >> (8 * ((j) & 3) - 3)) & 0x7F8u : (wd[(j) >> 2] << 3) & 0x7F8u)
+#define EC_B8(j) (((j) & 3) ? (wd[(j) >> 2] >> (8 * ((j) & 3) - 3)) & 0x7F8u : ec_byte0_x8(wd[(j) >> 2]))
     // (!FR) per input dword: four codes (+ the pad at a string's last byte)
     // -> two pairs {pc, pl} (MSB-aligned, < 32 bits) -> one quad {qh:qo, ql};
     // (FR) per byte pair: {ph:po} (MSB-aligned, <= 64 bits), length pq
@@ -798,7 +832,7 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
         }
         const uint32_t pl0 = l[0] + l[1], pl1 = l[2] + l[3];
         const uint32_t pc0 = c[0] | (c[1] >> l[0]), pc1 = c[2] | (c[3] >> l[2]);
-        plx = max(plx, max(pl0, pl1));
+        plx |= pl0 | pl1;  // (a pair of 32 bits or more sets a bit above the fifth)
         ql[m] = pl0 + pl1;
         qh[m] = pc0 | (pc1 >> pl0);
         qo[m] = __builtin_amdgcn_alignbit(pc1, 0u, pl0);
@@ -830,7 +864,10 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
     for (int m = 0; m < (FR ? 8 : 4); ++m) S += ql[m];
     S = act ? S : 0u;
     // a pair of 32 (FR: 64) bits or more: bytewise
-    const bool longp = __ballot(act && plx > (FR ? 64u : 31u)) != 0;
+    // (two compares and a scalar AND: __ballot of the conjunction went
+    // through a select and a third compare)
+    const bool longp = (__builtin_amdgcn_ballot_w64(plx > (FR ? 64u : 31u)) &
+                        __builtin_amdgcn_ballot_w64(act)) != 0;
     // ---- the first chunk's bytes before A go before the wave's first bit
     // (no pads there)
     uint32_t RA = 0;
@@ -848,11 +885,12 @@ __global__ __launch_bounds__(WG, EC_WPE) void k_encode(const uint8_t *__restrict
     const uint32_t ib0 = (uint32_t)(G0 + x - 32ull * WB) + 32u * EC_M + (Sinc - S) + X0 - RA;
     if (act) {
       if (!longp) {
-        uint32_t b = ib0;
+        HD_CHECK(((ib0 + S) >> 5) + 2u < RW, 0x101u);  // (the chunk's last run ends before ib0 + S)
+        uint32_t ba = ec_bit_addr(img, ib0);
 #pragma unroll
         for (int m = 0; m < (FR ? 8 : 4); ++m) {
-          ec_or3(img, b, qh[m], qo[m], RW);
-          b += ql[m];
+          ec_or3_at(ba, qh[m], qo[m]);
+          ba += ql[m];
         }
       } else {  // a code of <= 37 bits, MSB-aligned in 64; one dword at a time
         uint32_t b = ib0;
