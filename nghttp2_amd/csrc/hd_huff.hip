@@ -307,15 +307,6 @@ __global__ __launch_bounds__(WG) void k_scan_apply(uint32_t *__restrict__ offs, 
 }
 
 #define ENC_WAVES 4                  // waves per encode workgroup (tile = 256 strings)
-#ifndef EC_CNT_UNROLL
-// the count's wave loop: two chunk buffers, unrolled by two.  (Kept as a
-// switch: its other arm, the rolled loop, is the only reader of EC_CNT_PFD,
-// a depth the next A/Bs still override.)
-#define EC_CNT_UNROLL 1
-#endif
-#ifndef EC_CNT_PFD
-#define EC_CNT_PFD 2  // k_enc_count: rounds of chunks in flight per wave (4: no faster)
-#endif
 
 // bytes of the 7-bit-prefix integer n (count_encoded_length(n, 7))
 __device__ __forceinline__ uint32_t prefix7_len(uint32_t n) {
@@ -410,15 +401,15 @@ __device__ __forceinline__ uint32_t wave_string_bits(const uint8_t *__restrict__
     ok = c < c_end;
     return *reinterpret_cast<const uint4 *>(src + ((size_t)min(c, c_last) << 4));
   };
-#if EC_CNT_UNROLL
   // chunks two rounds ahead, in two buffers the loop (unrolled by two)
   // alternates: a buffer is reloaded only after its round has used it, so
   // no register copy of a load in flight makes the round wait for it.
-  // (Round 6: the rolled loop below rotated q[0] <- q[1] each round, and
-  // that copy of the load just issued waited for it, vmcnt(0) -- every
-  // round took a whole memory latency, whatever EC_CNT_PFD was.  Unrolled:
-  // count 37.1 vs 40.9 us on config 3, encode pair 123.4 vs 127.8, config
-  // 2 count 14.9 vs 15.4, outputs equal; profiles/r06/ab/ab_count_unroll.log)
+  // (Round 6: the rolled loop this replaced kept its chunks in a register
+  // array rotated each round, q[0] <- q[1], and that copy of the load just
+  // issued waited for it, vmcnt(0) -- every round took a whole memory
+  // latency, whether 2 or 4 rounds were in flight.  Unrolled: count 37.1 vs
+  // 40.9 us on config 3, encode pair 123.4 vs 127.8, config 2 count 14.9 vs
+  // 15.4, outputs equal; profiles/r06/ab/ab_count_unroll.log)
   bool oka, okb;
   uint4 qa = load(c0 + lane, oka), qb = load(c0 + 64u + lane, okb);
   for (uint32_t cb = c0; cb < c_end; cb += 128u) {
@@ -428,24 +419,6 @@ __device__ __forceinline__ uint32_t wave_string_bits(const uint8_t *__restrict__
     round(cb + 64u, qb, okb);
     qb = load(cb + 192u + lane, okb);
   }
-#else
-  // chunks are loaded EC_CNT_PFD rounds ahead
-  uint4 q[EC_CNT_PFD];
-#pragma unroll
-  for (uint32_t d = 0; d < EC_CNT_PFD; ++d) {
-    q[d] = make_uint4(0, 0, 0, 0);
-    if (c0 + 64u * d + lane < c_end) q[d] = *reinterpret_cast<const uint4 *>(src + ((c0 + 64u * d + lane) << 4));
-  }
-  for (uint32_t cb = c0; cb < c_end; cb += 64u) {
-    const uint4 qv = q[0];
-#pragma unroll
-    for (uint32_t d = 0; d + 1 < EC_CNT_PFD; ++d) q[d] = q[d + 1];
-    q[EC_CNT_PFD - 1] = make_uint4(0, 0, 0, 0);
-    if (cb + 64u * EC_CNT_PFD + lane < c_end)
-      q[EC_CNT_PFD - 1] = *reinterpret_cast<const uint4 *>(src + ((cb + 64u * EC_CNT_PFD + lane) << 4));
-    round(cb, qv, true);
-  }
-#endif
   // an end at the last chunk's end (Z on a chunk boundary)
   if (!ga) Pa = Rc;
   if (!gb) Pb = Rc;
@@ -518,9 +491,7 @@ __global__ __launch_bounds__(EC_CNT_NT) void k_enc_count(const uint8_t *__restri
 // workgroup reads all of them, O(tiles^2) L2 reads: 8.6 GB for 16M strings)
 // costs more than this launch.  A poisoned tile (0xFFFFFFFF) pushes every
 // later prefix past the uint32 offsets, as the in-kernel sum does.
-#ifndef EC_SCAN_TILES
 #define EC_SCAN_TILES 16384u
-#endif
 __global__ __launch_bounds__(1024) void k_tile_prefix64(const uint32_t *__restrict__ tiles, uint32_t nt,
                                                         uint64_t *__restrict__ pre) {
   __shared__ uint64_t wsum[16];
@@ -544,9 +515,7 @@ __global__ __launch_bounds__(1024) void k_tile_prefix64(const uint32_t *__restri
   }
 }
 
-#ifndef EC_WPE
 #define EC_WPE 4  // k_encode: waves per SIMD the register budget is sized for
-#endif
 #define EC_M 16u                    // image margin (words): >= 15 bytes x 30 bits
 #define EC_RW (EC_M + 1024u + 32u)  // + 1 KB at <= 32 bits a byte + carry + bytes past Z
 // FR: + the wave's literal prefixes and pads (64 x (6 x 8 + 7) bits)
@@ -1535,36 +1504,17 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
 // ---------------------------------------------------------------------------
 // decode_batch_auto: the item decoder and its helpers
 // ---------------------------------------------------------------------------
-#ifndef DD_OV
 #define DD_OV 20u  // warm-up bytes of a later item (round 2, 24: 314.2 vs 306.5 us on config 3;
                    // round 3 with overshooting warm-ups, 16/18/22: 312.4/308.9/304.8 vs 300.8)
-#endif
-#ifndef DD_TASK_W
 #define DD_TASK_W 32u  // a string's weight in bytes when balancing tasks over workgroups
-#endif
 #define DD_NONE 0xFFFFFFFCu  // a round's carried exit: the last item ended its string
-#ifndef DD_IW64
 #define DD_IW64 16
-#endif
-#ifndef DD_BI64
 #define DD_BI64 2304u
-#endif
-#ifndef DD_BI40
 #define DD_BI40 0u
-#endif
-#ifndef DD_IW40
 #define DD_IW40 16
-#endif
-#ifndef DD_LB40
 #define DD_LB40 13  // lookup bits of the long-string instance
-#endif
-#ifndef DD_LB64
 #define DD_LB64 13  // lookup bits of the short-string instance
-#endif
-#ifndef DD_IP40
 #define DD_IP40 40u  // piece bytes of the long-string instance
-#endif
-#ifndef DD_IP64
 // piece bytes of the short-string instance.  Round 6: 96 (was 64): a string
 // of 65-96 encoded bytes is one item instead of two, so a task of short
 // strings with a few such strings among them needs one budgeted round, not a
@@ -1572,58 +1522,31 @@ __global__ __launch_bounds__(DEC_NT) void k_decode(const uint8_t *__restrict__ s
 // reach 83 bytes: 98.7 -> 59.9 us; config 2, all <= 64 bytes: 43.6 / 43.7;
 // 128: 60.1 / 44.2; profiles/r06/ab/ab_piece96.log)
 #define DD_IP64 96u
-#endif
-#ifndef DD_TS64
 #define DD_TS64 64u  // strings per task unit of the 64-byte instance
-#endif
-#ifndef DD_TK64
 #define DD_TK64 1u
-#endif
-#ifndef DD_TS40
 #define DD_TS40 32u  // strings per task unit of the 40-byte instance
-#endif
-#ifndef DD_TK40
 #define DD_TK40 2u  // units per task (the workgroup's last ones: one unit)
-#endif
-#ifndef DD_TAILU
 #define DD_TAILU 2u  // the workgroup's last DD_TAILU x waves units are claimed singly
-#endif
-#ifndef DD_SK40
-#define DD_SK40 2u  // the 40-byte instance's serving period in pairs (dd_run SLOWK; unused while DD_LD40 defers its long codes)
-#endif
-#ifndef DD_DIRECT_MIN
 #define DD_DIRECT_MIN 4u  // lanes of a round with long codes that switch the wave's next round to direct
-#endif
-#ifndef DD_DIRECT_KEEP
 #define DD_DIRECT_KEEP 4u  // ... and to keep it on for the round after
-#endif
-#ifndef DD_LD40
-#define DD_LD40 1u  // the 40-byte instance's long codes in the pair loop (dd_run LDEF): 0 served, 1 deferred, 2 deferred in two-pair trips
-#endif
-#ifndef DD_LDW40
-#define DD_LDW40 1u  // ... and in its warm-ups too (0: warm-ups keep the served form)
-#endif
-#ifndef DD_DEFW
 #define DD_DEFW 15u  // a deferred long code of up to DD_DEFW bits is followed by the pair's second lookup
-#endif
-#ifndef DD_SK64
-#define DD_SK64 1u  // the 64-byte instance (config 5's 30-bit codes everywhere): every pair
-#endif
 
 // A decoder instance of k_decode_items: IP piece bytes (a longer string is
 // cut into items of IP bytes), IW waves per workgroup, LB lookup bits, BI a
-// round's input-byte budget (0: none, a round is 64 items), SK the period in
-// pairs at which dd_run serves long codes, tasks of TK units of TS strings.
+// round's input-byte budget (0: none, a round is 64 items), tasks of TK units
+// of TS strings, LD how dd_run's pair loop takes a code past the lookup, in
+// the items and in their warm-ups: deferred to the lane's next pair (true),
+// or served in the pair, with the per-round direct mode (false).
 // decode_batch_auto's two (see decode_items for the pick and its measurements):
 struct DecHeader {  // header strings: whole strings as items, budgeted rounds
-  static constexpr uint32_t IP = DD_IP64, BI = DD_BI64, SK = DD_SK64, TS = DD_TS64, TK = DD_TK64;
+  static constexpr uint32_t IP = DD_IP64, BI = DD_BI64, TS = DD_TS64, TK = DD_TK64;
   static constexpr int IW = DD_IW64, LB = DD_LB64;
-  static constexpr uint32_t LD = 0, LDW = 0;
+  static constexpr bool LD = false;  // (config 5's 30-bit codes everywhere: served every pair, or direct)
 };
 struct DecLong {  // long values: 40-byte pieces, ranges balanced by weight
-  static constexpr uint32_t IP = DD_IP40, BI = DD_BI40, SK = DD_SK40, TS = DD_TS40, TK = DD_TK40;
+  static constexpr uint32_t IP = DD_IP40, BI = DD_BI40, TS = DD_TS40, TK = DD_TK40;
   static constexpr int IW = DD_IW40, LB = DD_LB40;
-  static constexpr uint32_t LD = DD_LD40, LDW = DD_LDW40 ? DD_LD40 : 0u;
+  static constexpr bool LD = true;
 };
 
 // The output region of an item of `bytes` input bytes (<= (8 bytes + 29) / 5
@@ -1738,10 +1661,13 @@ struct DDRun {
 // The 40-byte instance (LDEF) then reads it from the leading-ones table as
 // the lane's next pair's first read (deferred: no serving block, no third
 // dependent read, no further stall; `pair_def` below).  The 64-byte instance
-// sends it through long_entry in a block the wave runs every SLOWK-th pair,
-// or decodes it directly (kDirect); there, one that would pass the string
-// end is its tail and leaves the fast loop.  The last bits go through checked steps,
+// sends it through long_entry in a block at the pair's end (`pair` below),
+// or, in a round the caller made `direct`, decodes a pair's first code
+// there in the pair's second read; one that would pass the string end is its
+// tail and leaves the fast loop.  The last bits go through checked steps,
 // which also settle the tail: the undecoded t < 30 bits.
+// *nslow counts the long codes the served pairs met, for the caller's choice
+// of `direct`; the deferred form has no direct mode and counts nothing.
 #define DD_ADV(U)                                                        \
   do {                                                                   \
     const uint32_t u_ = (U);                                             \
@@ -1752,15 +1678,10 @@ struct DDRun {
     kw += t_ ? 1 : 0;                                                    \
     N = ib((uint32_t)kw + 2u);                                           \
   } while (0)
-// PAIRS: only the fast pairs, none starting past `lim` (no careful steps):
-// bp stops at a codeword boundary on the way, for a caller that records it
-// and goes on with another dd_run.
-template <class Sink, bool SYNC = false, bool PAIRS = false, uint32_t SLOWK = 1, uint32_t LDEF = 0,
-          class TT, class IN>
+template <class Sink, bool SYNC, bool LDEF, class TT, class IN>
 __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
                                         uint32_t bstop, uint32_t bend, Sink &sink,
-                                        int32_t lim = INT32_MAX, bool direct = false,
-                                        uint32_t *nslow = nullptr) {
+                                        bool direct, uint32_t *nslow) {
   DDRun r;
   r.at_end = false;
   r.t = 0;
@@ -1780,8 +1701,7 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   constexpr int32_t kEndB = (LDEF && kSecond + TT::BITS < 30) ? 30 : kSecond + TT::BITS;
   static_assert(!LDEF || (DD_DEFW + TT::BITS < 32u && DD_DEFW >= (uint32_t)TT::BITS),
                 "a pair advances < 32 bits (DD_ADV); a lookup entry is never taken for a long one");
-  int32_t G2 = min((int32_t)bstop - (SYNC ? 1 : kStopB), (int32_t)bend - kEndB);
-  if (PAIRS) G2 = min(G2, lim);
+  const int32_t G2 = min((int32_t)bstop - (SYNC ? 1 : kStopB), (int32_t)bend - kEndB);
   // (SYNC) the last pair: start (as nq), entries, slow code
   uint32_t pb = ~(bp - 1u), le1 = 0, le2 = 0, ls = 0;
   // (bp = 0: A is the dword before the staged words, never inside a window;
@@ -1795,38 +1715,38 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   // the window words in before the loop (else the loop head waits for every
   // LDS access in flight, the prefetch of N included, each pair)
   wait_lgkmcnt0();
-  // a code longer than the lookup inside the pair loop: decode it, or leave
-  // the pair loop at EOS (failed) or at the string's tail (the careful steps
-  // find it again).  Predicated, with `failed` a VGPR flag: the nested
-  // branches this replaces left exec-mask merges (≈7 SALU) in every pair,
-  // taken or not (round 4: config 3 decode 277.6 -> 258.1 us, config 5
-  // 135.1 -> 130.0, config 2 48.8 -> 47.8).  SLOWK > 1: a lane that meets a
-  // long code stalls (its entries use no bits and emit nothing) and the
-  // long codes are served every SLOWK-th pair, so the wave pays the slow
-  // path's dependent reads once for several lanes' codes (config 3, k = 2:
-  // 258.1 -> 253.0 us; the 64-byte instance, which serves config 5's 30-bit
-  // codes everywhere, keeps k = 1)
-  // The fast pairs run at raised wave priority: the SIMD issues their
-  // dependent chain's VALU before other waves' staging, scans and stores
-  // (config 3 decode 294.1 vs 297.7 us, config 2 50.6 vs 52.2; priority 3,
-  // or priority over the whole run with its careful steps: no better)
-  // direct (the 64-byte instance only, SLOWK == 1, chosen per round by the
-  // caller: a wave whose last round met many long codes, as config 5's
-  // strings of 28- and 30-bit codes do): a window whose first code is past
-  // the lookup (e1 = 0) reads that code from the leading-ones table as the
-  // pair's second read (its address computed while e1 is in flight), so the
-  // pair decodes it instead of stalling for the slow path; a long code that
-  // would pass the string end, or EOS, stops the lane for the careful
-  // steps.  (Round 5: always on it took config 5 from 103.5 to 94.2 us but
-  // config 2, which has no such codes, from 41.6 to 47.4; behind a wave
-  // ballot per pair 97.5 / 43.8.  The loop is compiled both ways; the
-  // caller switches a wave per round by the count of long codes its lanes
-  // met (*nslow: slow-path runs plus direct decodes): sticky per wave,
-  // config 2 +0.8 us; per round, on at 4 lanes and kept at 4, config 5
-  // 100.9 -> 96.4 with config 2 41.7 -> 41.9, one box, 16 rounds each.)
-  uint32_t it = 0, nlong = 0;
-  // one fast pair; slow: this pair may serve a long code (the slow path)
-  auto pair = [&](auto dir, bool slow) {
+  // The pair loop is one of two, each one pair per trip, at raised wave
+  // priority: the SIMD issues the pairs' dependent chain's VALU before other
+  // waves' staging, scans and stores (config 3 decode 294.1 vs 297.7 us,
+  // config 2 50.6 vs 52.2; priority 3, or priority over the whole run with
+  // its careful steps: no better).
+  //
+  // served (`pair`, the 64-byte instance): two lookups, then a code longer
+  // than the lookup is decoded in the slow path at the pair's end, or the
+  // lane leaves the pair loop at EOS (failed) or at the string's tail (the
+  // careful steps find it again).  Predicated, with `failed` a VGPR flag: the
+  // nested branches this replaces left exec-mask merges (≈7 SALU) in every
+  // pair, taken or not (round 4: config 3 decode 277.6 -> 258.1 us, config 5
+  // 135.1 -> 130.0, config 2 48.8 -> 47.8).  Every pair serves: config 5's
+  // 30-bit codes are everywhere (serving every second pair paid on the
+  // 40-byte instance alone, config 3 258.1 -> 253.0 us, until that one
+  // deferred its long codes: removed).
+  // direct (chosen per round by the caller: a wave whose last round met many
+  // long codes, as config 5's strings of 28- and 30-bit codes do): a window
+  // whose first code is past the lookup (e1 = 0) reads that code from the
+  // leading-ones table as the pair's second read (its address computed while
+  // e1 is in flight), so the pair decodes it instead of stalling for the
+  // slow path; a long code that would pass the string end, or EOS, stops the
+  // lane for the careful steps.  (Round 5: always on it took config 5 from
+  // 103.5 to 94.2 us but config 2, which has no such codes, from 41.6 to
+  // 47.4; behind a wave ballot per pair 97.5 / 43.8.  The loop is compiled
+  // both ways; the caller switches a wave per round by the count of long
+  // codes its lanes met (*nslow: slow-path runs plus direct decodes): sticky
+  // per wave, config 2 +0.8 us; per round, on at 4 lanes and kept at 4,
+  // config 5 100.9 -> 96.4 with config 2 41.7 -> 41.9, one box, 16 rounds
+  // each.)
+  uint32_t nlong = 0;
+  auto pair = [&](auto dir) {
     constexpr bool kDirect = decltype(dir)::value;
     {
       const uint32_t w = __builtin_amdgcn_alignbit(A, B, nq);
@@ -1855,14 +1775,14 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
       DD_ADV(U1 + U2);
       // (the slow path behind one uniform branch, predicated per lane: the
       // wave takes it whenever one of its lanes met a long code -- on config
-      // 3's bytes nearly every serving pair -- and the exec-mask save and
-      // restore of a divergent branch, which this replaced, cost every time.
-      // Round 6: config 3 decode 213.5 / 207.4 vs 216.3 / 210.3 us, configs
-      // 2 and 5 -0.7 / -0.3 %, outputs equal;
-      // profiles/r06/ab/ab_slow_uniform.log)
+      // 3's bytes, which this loop still decoded then, nearly every serving
+      // pair -- and the exec-mask save and restore of a divergent branch,
+      // which this replaced, cost every time.  Round 6: config 3 decode
+      // 213.5 / 207.4 vs 216.3 / 210.3 us, configs 2 and 5 -0.7 / -0.3 %,
+      // outputs equal; profiles/r06/ab/ab_slow_uniform.log)
       {
         // (an e1 of 0 stalls e2 too; direct: e1 = 0 was decoded or stopped)
-        const bool need = slow && e2 == 0u && (!kDirect || e1 != 0u);
+        const bool need = e2 == 0u && (!kDirect || e1 != 0u);
         if (__ballot(need)) {
           const uint32_t rem_ = bend - (~nq + 1u);
           const uint32_t e_ = long_entry(T, __builtin_amdgcn_alignbit(A, B, nq), rem_);
@@ -1880,11 +1800,12 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
       }
     }
   };
-  // deferred (LDEF): a lane whose second lookup returned 0 -- its first one
-  // did too, then, the window unchanged -- keeps the index of the long code
-  // at its new window, computed at the pair's end off the next pair's chain,
-  // and its next pair's first read goes to the leading-ones table instead
-  // of the lookup: no serving block, no third dependent read, no stall.  The
+  // deferred (`pair_def`, LDEF: the 40-byte instance, items and warm-ups): a
+  // lane whose second lookup returned 0 -- its first one did too, then, the
+  // window unchanged -- keeps the index of the long code at its new window,
+  // computed at the pair's end off the next pair's chain, and its next
+  // pair's first read goes to the leading-ones table instead of the
+  // lookup: no serving block, no third dependent read, no stall.  The
   // entry has the lookup's layout (one symbol, used = L1 = its length).  A
   // pair starts at most 30 bits before the string end, so the long code
   // ends inside the string; EOS (30 ones: the table's last two rows) is not
@@ -1902,8 +1823,9 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
   // the serving form's 216.7 / 214.6 / 213.4 us in three interleaved sets,
   // outputs equal, configs 2 and 5 flat; with long_index, a flag and the
   // select at the pair's head 208.5 / 211.3 / 213.0 vs 210.8 / 213.1 / 214.1;
-  // two-pair trips 200.7 / 197.6 / 197.5; warm-ups left on the serving form
-  // 201.1 / 198.1 / 200.0 -- profiles/long_codes_deferred/)
+  // two pairs per trip 200.7 / 197.6 / 197.5; warm-ups left on the serving
+  // form 201.1 / 198.1 / 200.0: both removed since --
+  // profiles/long_codes_deferred/)
   // (one table base and an index select: the tables are adjacent words)
   static_assert(offsetof(TT, lut) == 0 && offsetof(TT, long1) == sizeof(uint32_t) << TT::BITS, "tables adjacent");
   const uint32_t *tw = T.lut;
@@ -1935,48 +1857,23 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
     di = (lg & !eos) ? li : dw >> (32 - TT::BITS);
     nG = (lg & eos) ? INT32_MAX : nG;
   };
+  // (one pair per trip in both forms.  The served loop as two pairs per trip:
+  // config 2 44.0 vs 42.8 us, config 5 61.9 vs 60.8; the deferred one: the
+  // figures above -- the two-pair trip paid only while the 40-byte instance
+  // served its long codes every second pair)
+  // (the early return stays: as if / else the same two loops compile to other
+  // register assignments in the long instance)
   auto pairs = [&](auto dir) {
-    constexpr bool kDirect = decltype(dir)::value;
-    if constexpr (LDEF != 0u) {
-      // (LDEF 2: two pairs per trip for the loop's exec-mask bookkeeping
-      // alone; the first takes at most 30 bits)
-      if (LDEF == 2u) {
-        while ((int32_t)nq - 30 >= nG) {
-          pair_def();
-          pair_def();
-        }
-      }
+    if constexpr (LDEF) {
       while ((int32_t)nq >= nG) pair_def();
       return;
     }
-    if constexpr (SLOWK == 2u && !kDirect) {
-      // SLOWK 2 as two pairs per trip, the second one serving long codes:
-      // the slow-code period is static (no counter parity in SALU) and the
-      // loop's exec-mask bookkeeping is paid once per two pairs (round 6:
-      // config 3 decode 209.9 / 208.6 / 217.4 vs 213.0 / 210.0 / 220.8 us in
-      // three interleaved sets, outputs equal; configs 2 and 5 flat).  A trip
-      // starts only where its second pair keeps the single pair's bound (the
-      // first takes <= 2 BITS bits and serves no long code); the last pairs,
-      // each serving long codes, run one at a time.  (Four pairs per trip,
-      // bound 4 BITS + BITS + 30: 216.1 vs 210.0; the SLOWK 1 loop as two
-      // pairs, bound BITS + 30: config 2 44.0 vs 42.8, config 5 61.9 vs 60.8
-      // -- profiles/r06/ab/ab_pair_trips.log)
-      while ((int32_t)nq - (int32_t)(2 * TT::BITS) >= nG) {
-        pair(dir, false);
-        pair(dir, true);
-      }
-      while ((int32_t)nq >= nG) pair(dir, true);
-      return;
-    }
-    // (any other period: a pair counter's parity, which the trips above
-    // replaced for SLOWK 2)
-    while ((int32_t)nq >= nG) {
-      ++it;
-      pair(dir, SLOWK == 1u || (it & (SLOWK - 1u)) == 0u);
-    }
+    while ((int32_t)nq >= nG) pair(dir);
   };
   __builtin_amdgcn_s_setprio(1);
-  if (SLOWK == 1u && direct) pairs(std::true_type{});
+  // (the deferred form has no direct mode: k_decode_items raises `direct`
+  // for the served instance only, and `pairs` ignores it under LDEF)
+  if (direct) pairs(std::true_type{});
   else pairs(std::false_type{});
   __builtin_amdgcn_s_setprio(0);
   if (nslow) *nslow += nlong;
@@ -1991,11 +1888,6 @@ __device__ __forceinline__ DDRun dd_run(const TT &T, const IN &ib, uint32_t &bp,
     const uint32_t c3 = c2 + (le2 ? E_L1(le2) : ls), c4 = c2 + (le2 ? E_USED(le2) : ls);
     bp = c1 >= bstop ? c1 : c2 >= bstop ? c2 : c3 >= bstop ? c3 : c4;
     r.failed = false;
-    return r;
-  }
-  if (PAIRS) {
-    sink.flush();
-    r.failed = failed;
     return r;
   }
   if (SYNC) {
@@ -2183,7 +2075,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
                                                            int32_t *__restrict__ status,
                                                            uint16_t *__restrict__ fstate_out,
                                                            uint8_t *__restrict__ flags_out) {
-  constexpr uint32_t IP = C::IP, BI = C::BI, SK = C::SK, TS = C::TS, TK = C::TK;
+  constexpr uint32_t IP = C::IP, BI = C::BI, TS = C::TS, TK = C::TK;
   constexpr int IW = C::IW;
   __shared__ DIShared<C> S;
   constexpr uint32_t kSpan = DI<C>::SPAN, kPF = DI<C>::PF;
@@ -2342,7 +2234,8 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
   uint32_t task_k = next_k;
   load_offs(t_first < t_hi ? t_first : ntask, task_k, na_l, nb_l);
   uint32_t next_task = t_hi;
-  // direct long codes (the 64-byte instance, see dd_run): on for the wave's
+  // direct long codes (the served instance, !C::LD, only: the deferred one
+  // never raises dmode and counts nothing in nslow; see dd_run): on for the wave's
   // next round when DD_DIRECT_MIN of this round's lanes met a code past the
   // lookup (slow-path runs, or direct decodes of such codes; DD_DIRECT_KEEP
   // of them to stay on).  (Never direct, always direct and a ballot per pair
@@ -2498,8 +2391,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
       if (spec) {
         uint32_t bp = 8u * (s - DD_OV - IBX);
         DiscardSink dk;
-        const DDRun rw = dd_run<DiscardSink, true, false, SK, C::LDW>(S.T, inp, bp, bs, bend, dk,
-                                                                      INT32_MAX, dmode, &nslow);
+        const DDRun rw = dd_run<DiscardSink, true, C::LD>(S.T, inp, bp, bs, bend, dk, dmode, &nslow);
         entry = bp;
         dead = rw.failed;
       }
@@ -2512,7 +2404,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
       // same inlined decoder as its re-decodes)
       constexpr bool kMerge = BI == 0;
       if (valid && !dead && !kMerge)
-        rr = dd_run<DISink, false, false, SK, C::LD>(S.T, inp, bp, bstop, bend, sk, INT32_MAX, dmode, &nslow);
+        rr = dd_run<DISink, false, C::LD>(S.T, inp, bp, bstop, bend, sk, dmode, &nslow);
       uint32_t my_exit = rr.failed ? XFAIL : bp;
       uint32_t my_entry = dead ? XUNKNOWN : entry;
       uint32_t c0 = sk.count();
@@ -2526,7 +2418,7 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
           if (run_) {
             DISink s3(my_ob HD_LIM(my_ob + my_rb));
             uint32_t bq = start;
-            rr = dd_run<DISink, false, false, SK, C::LD>(S.T, inp, bq, bstop, bend, s3, INT32_MAX, dmode, &nslow);
+            rr = dd_run<DISink, false, C::LD>(S.T, inp, bq, bstop, bend, s3, dmode, &nslow);
             my_exit = rr.failed ? XFAIL : bq;
             c0 = s3.count();
           }
@@ -2551,14 +2443,14 @@ __global__ __launch_bounds__(WAVE * C::IW) void k_decode_items(const uint8_t *__
             run_ = true;
           } else {
             uint32_t bq = pred;
-            rr = dd_run<DISink, false, false, SK, C::LD>(S.T, inp, bq, bstop, bend, s3, INT32_MAX, dmode, &nslow);
+            rr = dd_run<DISink, false, C::LD>(S.T, inp, bq, bstop, bend, s3, dmode, &nslow);
             my_exit = rr.failed ? XFAIL : bq;
             c0 = s3.count();
           }
           my_entry = pred;
         }
       }
-      if (SK == 1u) {
+      if (!C::LD) {
         dmode = __builtin_popcountll(__ballot(nslow != 0u)) >=
                 (dmode ? DD_DIRECT_KEEP : DD_DIRECT_MIN);
         nslow = 0;
