@@ -58,7 +58,7 @@ namespace dev {
 }  // namespace dev
 
 namespace host {
-#define HD_TBL static
+#define HD_TBL static constexpr  // (constexpr: the encode's static_assert reads the code lengths)
 #include "hd_huff_tables.inc"
 #undef HD_TBL
 }  // namespace host
@@ -333,60 +333,112 @@ __device__ __forceinline__ uint32_t prefix7_byte(uint32_t n, uint32_t h, uint32_
 // Pass 1 (lib/nghttp2_hd_huffman.c:34-43): code bits per string.  With P(x)
 // = the code bits of the wave's bytes from its first chunk up to byte x, a
 // string's bits are P(b) - P(a): each lane sums its chunk's code lengths
-// (in-chunk exclusive prefixes to LDS, 16 bits a byte), a wave scan places
+// (in-chunk exclusive prefixes to LDS, one byte a byte), a wave scan places
 // the chunks, and every string lane reads P at its two ends.  Bytes before
 // A or past Z in the edge chunks add the same amount to both ends.
 // FR (emit_string, lib/nghttp2_hd.c:1001-1044): the tile sums are of the
 // string LITERALS' bytes, prefix7_len(P) + P with P = min(E, R) (H = E < R).
+
+// One-byte prefixes.  A code is at most 30 bits (RFC 7541 appendix B), so
+// within an 8-byte half chunk the exclusive prefix at byte 7 is at most
+// 7 x 30 = 210 and the half's total at most 8 x 30 = 240: both fit a byte,
+// where a whole chunk's (up to 480) do not.  Any table whose codes are at
+// most 31 bits fits (8 x 31 = 248); the assertion below refuses the build
+// for another, and so does the table generator.  A lane's 16 bytes, byte x
+// for in-chunk position x:
+//   byte 0       0 (the first half's exclusive prefix at its first byte)
+//   bytes 1..7   the prefixes within the first half
+//   byte 8       the first half's total (the second half's prefix at its
+//                first byte is 0 too, so its slot is free for it)
+//   bytes 9..15  the prefixes within the second half
+// and the in-chunk prefix at x is byte[x] + (x > 8 ? byte[8] : 0).
+constexpr bool ec_code_lengths_fit_a_byte() {
+  for (int i = 0; i < 257; ++i)
+    if (host::hd_huff_enc_len[i] > 31) return false;
+  return true;
+}
+static_assert(ec_code_lengths_fit_a_byte(),
+              "wave_string_bits keeps the code bits of 8 bytes in one byte: no code may pass 31 bits");
+
+// d's byte SEL plus l (a sum below 256 leaves the other bytes zero), and the
+// same sum written to d's byte SEL + 1 with d's other bytes kept: the add
+// and the packing of a prefix byte in one instruction each.
+#define EC_BYTE_PLUS(SEL)                                                                      \
+  __device__ __forceinline__ uint32_t ec_byte##SEL##_plus(uint32_t d, uint32_t l) {            \
+    uint32_t r;                                                                                \
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_" #SEL    \
+        " src1_sel:DWORD"                                                                      \
+        : "=v"(r)                                                                              \
+        : "v"(d), "v"(l));                                                                     \
+    return r;                                                                                  \
+  }
+#define EC_BYTE_NEXT(SEL, TO)                                                                  \
+  __device__ __forceinline__ uint32_t ec_byte##SEL##_next(uint32_t d, uint32_t l) {            \
+    asm("v_add_u32_sdwa %0, %0, %1 dst_sel:BYTE_" #TO " dst_unused:UNUSED_PRESERVE"            \
+        " src0_sel:BYTE_" #SEL " src1_sel:DWORD"                                               \
+        : "+v"(d)                                                                              \
+        : "v"(l));                                                                             \
+    return d;                                                                                  \
+  }
+EC_BYTE_PLUS(0)
+EC_BYTE_PLUS(3)
+EC_BYTE_NEXT(0, 1)
+EC_BYTE_NEXT(1, 2)
+EC_BYTE_NEXT(2, 3)
+#undef EC_BYTE_PLUS
+#undef EC_BYTE_NEXT
+
 // The code bits of a wave's 64 strings (string l in lane l: bytes [a_l,
 // b_l)): each lane sums its aligned 16-byte chunk's code lengths (lenT in
-// LDS, one byte per entry) and writes its in-chunk prefixes (16 bits a byte)
-// to the wave's LDS scratch pr (512 words); one wave scan places the chunks,
-// and every string lane reads P at its two ends.  Shared by k_enc_count and
-// the single-tile k_encode.
+// LDS, one byte per entry) and writes its in-chunk prefixes (the 16 bytes
+// above) to the wave's LDS scratch pr (256 words, byte r of the round at
+// byte r); one wave scan places the chunks, and every string lane reads P
+// at its two ends.  Shared by k_enc_count and the single-tile k_encode.
 __device__ __forceinline__ uint32_t wave_string_bits(const uint8_t *__restrict__ src, uint32_t a_l,
                                                      uint32_t b_l, bool sl, uint32_t nstr,
                                                      const lds_u8 *lenT, lds_u32 *pr, uint32_t lane) {
   const uint32_t A = __builtin_amdgcn_readfirstlane(a_l);
   const uint32_t Z = __builtin_amdgcn_readlane(b_l, nstr - 1u);
   const uint32_t c0 = A >> 4, c_end = (Z + 15u) >> 4;
-  const lds_u16 *pr16 = (const lds_u16 *)pr;
+  const lds_u8 *pr8 = (const lds_u8 *)pr;
+  // the second byte an end reads: the first half's total (byte 8) for an
+  // end past in-chunk position 8, else byte 0, which is always 0.  Chunks
+  // are aligned, so an end's in-chunk position is the same in every round,
+  // and so is the distance back from its own byte to that one.
+  const uint32_t da = (a_l & 15u) - ((a_l & 15u) > 8u ? 8u : 0u);
+  const uint32_t db = (b_l & 15u) - ((b_l & 15u) > 8u ? 8u : 0u);
   uint32_t Rc = 0, Pa = 0, Pb = 0;
   bool ga = false, gb = false;
   // one round: the 64 chunks from chunk cb, this lane's in qv
   auto round = [&](uint32_t cb, const uint4 &qv, bool ok) {
     const uint32_t base = cb << 4;
     const uint32_t wd[4] = {ok ? qv.x : 0u, ok ? qv.y : 0u, ok ? qv.z : 0u, ok ? qv.w : 0u};
-    uint32_t run = 0, pk[8];
+    uint32_t L[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t L = lenT[(wd[j >> 2] >> (8 * (j & 3))) & 0xFFu];
-      if (j & 1) pk[j >> 1] |= run << 16; else pk[j >> 1] = run;
-      run += L;
-    }
-    u32x4 v0, v1;
-    v0.x = pk[0]; v0.y = pk[1]; v0.z = pk[2]; v0.w = pk[3];
-    v1.x = pk[4]; v1.y = pk[5]; v1.z = pk[6]; v1.w = pk[7];
-    // (the chunk's first and second 8 prefixes in two halves of pr: lane
-    // strides of 16 bytes, 4-way per 32 lanes -- the least 16-byte stores
-    // can take.  Lost to it: both halves side by side at pr + 8 lane, a
-    // 32-byte stride, 8-way.  Round 6: count 34.9 vs 37.0 us on config 3,
-    // 14.4 vs 15.2 on config 2, outputs equal;
-    // profiles/r06/ab/ab_count_split_prefixes.log)
-    *(lds_u32x4 *)(pr + 4u * lane) = v0;
-    *(lds_u32x4 *)(pr + 256u + 4u * lane) = v1;
+    for (int j = 0; j < 16; ++j) L[j] = lenT[(wd[j >> 2] >> (8 * (j & 3))) & 0xFFu];
+    // each half's running sum lives in the byte it was last written to: a
+    // prefix byte costs the one add that forms it
+    u32x4 v;
+    v.x = ec_byte2_next(ec_byte1_next(L[0] << 8, L[1]), L[2]);
+    v.y = ec_byte2_next(ec_byte1_next(ec_byte0_next(ec_byte3_plus(v.x, L[3]), L[4]), L[5]), L[6]);
+    v.z = ec_byte2_next(ec_byte1_next(ec_byte3_plus(v.y, L[7]) | L[8] << 8, L[9]), L[10]);
+    v.w = ec_byte2_next(ec_byte1_next(ec_byte0_next(ec_byte3_plus(v.z, L[11]), L[12]), L[13]), L[14]);
+    const uint32_t run = ec_byte0_plus(v.z, ec_byte3_plus(v.w, L[15]));
+    // (one 16-byte store at a lane stride of 16 bytes, 4-way per 32 lanes --
+    // the least a 16-byte store can take)
+    *(lds_u32x4 *)(pr + 4u * lane) = v;
     const uint32_t Sinc = wave_incl_scan(run), Sx = Sinc - run;
     wave_lds_sync();
     // the string ends in this round: P = chunk start + in-chunk prefix
-    // (byte r of the round: u16 r & 7 of chunk r >> 4, in half r & 8)
+    // (byte r of the round, plus the chunk's byte 0 or 8, da / db before it)
     const uint32_t ra = a_l - base, rb = b_l - base;
     const uint32_t xa = __shfl(Sx, (ra >> 4) & 63u, 64), xb = __shfl(Sx, (rb >> 4) & 63u, 64);
     if (sl && ra < 1024u) {
-      Pa = Rc + xa + pr16[((ra >> 4) << 3) | (ra & 7u) | ((ra & 8u) << 6)];
+      Pa = Rc + xa + pr8[ra] + pr8[ra - da];
       ga = true;
     }
     if (sl && rb < 1024u) {
-      Pb = Rc + xb + pr16[((rb >> 4) << 3) | (rb & 7u) | ((rb & 8u) << 6)];
+      Pb = Rc + xb + pr8[rb] + pr8[rb - db];
       gb = true;
     }
     Rc += __builtin_amdgcn_readlane(Sinc, 63);
@@ -437,7 +489,7 @@ __global__ __launch_bounds__(EC_CNT_NT) void k_enc_count(const uint8_t *__restri
                                                   uint32_t *__restrict__ tile_sums,
                                                   int bits_out) {
   __shared__ uint8_t lenT[256];
-  __shared__ alignas(16) uint32_t pre[EC_CNT_NT / 64][512];  // a round's prefixes (u16 per byte)
+  __shared__ alignas(16) uint32_t pre[EC_CNT_NT / 64][256];  // a round's prefixes (u8 per byte)
   __shared__ uint32_t red[2 * EC_CNT_NT / 64];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   if (threadIdx.x < 256) lenT[threadIdx.x] = dev::hd_huff_enc_len[threadIdx.x];

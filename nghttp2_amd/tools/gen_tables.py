@@ -74,6 +74,9 @@ def build():
     codes, order = canonical_codes()
     leaf = {(v, L): s for s, (v, L) in enumerate(codes)}
     maxlen = max(RFC7541_LEN)
+    # k_enc_count keeps the code bits of 8 consecutive bytes in one byte
+    # (wave_string_bits in csrc/hd_huff.hip): 8 codes of at most 31 bits
+    assert 8 * maxlen <= 255, "a code longer than 31 bits: the count's one-byte prefixes overflow"
     # A prefix (v, d) is an internal node iff some code longer than d starts
     # with it.  Collect internal prefixes, then number them in pre-order
     # (root, then the 0-subtree, then the 1-subtree).
