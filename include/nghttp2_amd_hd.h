@@ -1035,6 +1035,104 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_inflate_blocks(
     const uint32_t *conn_blk, nghttp2_amd_hd_nv *nva, size_t nva_cap, uint8_t *arena, size_t arena_cap, uint32_t *block_nv_off,
     int32_t *out_status, uint32_t *out_totals, void *workspace, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ */
+/* Device-resident inflaters: masks, tokens and HTTP verdicts on the GPU  */
+/* ------------------------------------------------------------------ */
+/*
+ * What nghttp2_amd_hd_inflate_blocks_http adds to nghttp2_amd_hd_inflate_blocks,
+ * for the fields nghttp2_amd_hd_dev_inflate_blocks left in device memory.  The
+ * call follows the replay on the stream and reads no count on the host.
+ *
+ *   nva, nva_cap, arena, block_nv_off[n+1], out_status[n], out_totals[4],
+ *   nblocks           : IN: the replay's outputs, as it left them
+ *   arena_bytes       : the arena's allocation (see the pool rule below)
+ *   nv_checks         : OUT, 2 * nva_cap bytes or NULL: nv_checks[2 k] is the
+ *                       NGHTTP2_AMD_CHECK_* mask of field k's name,
+ *                       nv_checks[2 k + 1] that of its value
+ *   nv_tokens         : OUT, nva_cap int32 or NULL: lookup_token of field k's
+ *                       name (NGHTTP2_AMD_TOKEN_NONE or NGHTTP2_TOKEN_*)
+ *   block_modes[n]    : IN: block i's NGHTTP2_AMD_HTTP_MODE_* bits
+ *   block_state[n]    : IN-OUT: the stream's state before block i, and after
+ *   nv_verdicts       : OUT, nva_cap int32 or NULL: field k's
+ *                       nghttp2_amd_hd_http_on_header result, run in order on
+ *                       its block's state
+ *   block_http[n]     : OUT or NULL: the block's result
+ *   workspace         : device scratch, 16-byte aligned, >= the size below
+ *
+ * The results are nghttp2_amd_hd_inflate_blocks_http's for the same fields:
+ * of every array the entries of the out_totals[0] emitted fields are written
+ * and no other.  After a block's first NGHTTP2_AMD_ERR_HTTP_HEADER its later
+ * fields get NGHTTP2_AMD_HTTP_NOT_EXAMINED and the state stops changing.
+ * block_http[i] is NGHTTP2_AMD_ERR_HTTP_HEADER if a field failed, else
+ * NGHTTP2_AMD_ERR_HTTP_MESSAGING if the block-end function of the mode
+ * (request or response; none for a TRAILER block) returns -1, else 0.  A block
+ * whose out_status is negative (NGHTTP2_AMD_ERR_HEADER_COMP, or the capacity
+ * rule's NGHTTP2_AMD_ERR_NOMEM) gets verdicts for the fields it emitted, no
+ * block end, and that status in block_http.
+ * The NULL rules are the host call's: nv_checks and nv_tokens are
+ * independent; nv_verdicts and block_http may be NULL; block_modes and
+ * block_state are both needed (else NGHTTP2_AMD_ERR_INVALID_ARGUMENT) unless
+ * all four are NULL, which computes masks and/or tokens only (no facts launch,
+ * no step).  An HTTP call computes masks and tokens in the workspace whether
+ * or not nv_checks and nv_tokens are given.  With all six NULL nothing is
+ * queued.
+ *
+ * Specific to the device:
+ * - When out_totals[2] != 0 on entry the replay wrote no field: the call
+ *   writes nothing and changes no state.  The test is made on the device.
+ *   (out_totals is the replay's output: a replay that did nothing because the
+ *   parse's totals[3] was set wrote none, so the caller clears out_totals, or
+ *   sets out_totals[2], ahead of such a chain.)
+ * - A block that no connection listed in the replay's conn_blk has undefined
+ *   results (its out_status was never written); no memory outside the arrays
+ *   is touched whatever the records hold.
+ * - The pool rule of the three batch kernels: arena is 16-byte aligned and
+ *   readable to align_up(out_totals[1], 16) + 16, and arena_bytes says how far
+ *   it is readable.  When arena_bytes is smaller than that (and the batch has
+ *   a field), no string is examined, nothing is written and no state changes.
+ *
+ * The workspace opens with a totals word, four uint32 the call's first kernel
+ * writes: {the fields examined, their arena bytes, NGHTTP2_AMD_HD_DEV_FIELDS_*
+ * bits, 0}; with a bit set the first two are 0.
+ * nghttp2_amd_hd_dev_fields_http_totals copies it to the host (synchronises
+ * `stream`).  Behind it, each part rounded up to 16 bytes, with c = nva_cap:
+ *   the interleaved view   uint32[2 c + 1] offsets, int32[2 c] lengths
+ *   the names view         uint32[c + 1], int32[c]
+ *   the values view        uint32[c + 1], int32[c]
+ *   the values' numbers    int64[c]
+ *   the values' facts      uint32[c]
+ *   the names' tokens      int32[c]
+ *   the masks              uint8[2 c]
+ * (nblocks adds nothing: no scratch is kept per block.)
+ *
+ * Up to six launches: k_field_views (a lane per field slot writes the three
+ * views: a slot at or past the field count gets offset = arena bytes and
+ * length -1, a string the batch kernels do not examine),
+ * nghttp2_amd_hd_check_fields_batch on the interleaved view,
+ * nghttp2_amd_hd_name_tokens_len_batch (no hash) on the names, k_field_publish
+ * (the masks and tokens of the emitted fields to nv_checks and nv_tokens; the
+ * batch kernels write every slot they are launched for, so they write to the
+ * workspace), nghttp2_amd_hd_http_facts_batch on the values, and
+ * k_http_blocks (a lane per block runs the step of csrc/hd_http.h over its
+ * fields and the block end behind them).  The grids are sized from nva_cap
+ * and nblocks; a workgroup past the field count does next to nothing.
+ *
+ * Device pointers, asynchronous on `stream`.  nblocks == 0 returns 0 and
+ * touches nothing.  A NULL nva or arena (with nva_cap > 0), block_nv_off,
+ * out_status, out_totals or workspace, an arena or workspace that is not
+ * 16-byte aligned, an nva_cap above INT32_MAX, or a workspace below the size
+ * is NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ */
+#define NGHTTP2_AMD_HD_DEV_FIELDS_NOT_REPLAYED 0x1u /* out_totals[2] was set: the replay wrote no field */
+#define NGHTTP2_AMD_HD_DEV_FIELDS_ARENA_SHORT 0x2u  /* arena_bytes is below the pool rule */
+NGHTTP2_AMD_EXTERN size_t nghttp2_amd_hd_dev_fields_http_workspace_size(size_t nva_cap, uint32_t nblocks);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_fields_http(
+    const nghttp2_amd_hd_nv *nva, size_t nva_cap, const uint8_t *arena, size_t arena_bytes,
+    const uint32_t *block_nv_off, const int32_t *out_status, const uint32_t *out_totals, uint32_t nblocks,
+    uint8_t *nv_checks, int32_t *nv_tokens, const uint8_t *block_modes, nghttp2_amd_hd_http_state *block_state,
+    int32_t *nv_verdicts, int32_t *block_http, void *workspace, size_t ws_bytes, void *stream);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_fields_http_totals(const void *workspace, uint32_t *totals, void *stream);
+
 /*
  * The host twin (no GPU call): the same walk over host arrays with the same
  * layouts, for ONE connection whose blocks are the batch's, in order.  hdr is

@@ -33,6 +33,7 @@ from .hd import (  # noqa: F401
     decode_length,
     lib,
     parse_block,
+    replay_annotated,
     replay_fields,
     lib_path,
     deflate_blocks,

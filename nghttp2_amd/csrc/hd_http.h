@@ -14,7 +14,8 @@
 // facts and number.
 //
 // Shared by the host function (nghttp2_amd_hd_http_facts), the inflater's
-// replay and the GPU kernel (k_http_facts, the class table staged in LDS).
+// replay and the GPU kernels (k_http_facts, the class table staged in LDS;
+// k_http_blocks of hd_fields.hip, which runs the step and the block ends).
 // Plain C++17, no HIP: included by .cpp and .hip sources alike.
 #ifndef NGHTTP2_AMD_HD_HTTP_H
 #define NGHTTP2_AMD_HD_HTTP_H
@@ -158,23 +159,27 @@ struct Field {
   int32_t token;
   uint32_t name_mask, value_mask, facts;
   int64_t number;
+  // the name's first byte where the caller holds it already (k_http_blocks
+  // loads it ahead of the step), else -1: it is read from `name`
+  int32_t name0 = -1;
 };
+HDHTTP_FN uint32_t first_byte(const Field &f) { return f.name0 >= 0 ? (uint32_t)f.name0 : f.name[0]; }
 
-inline bool check_pseudo_header(State *st, const Field &f, uint32_t flag) {  // :91-98
+HDHTTP_FN bool check_pseudo_header(State *st, const Field &f, uint32_t flag) {  // :91-98
   if ((st->http_flags & flag) || f.value_len == 0) return false;
   st->http_flags |= flag;
   return true;
 }
-inline bool check_header_value(uint32_t mode, const Field &f) {  // :178-186
+HDHTTP_FN bool check_header_value(uint32_t mode, const Field &f) {  // :178-186
   return (f.value_mask &
           ((mode & NGHTTP2_AMD_HTTP_MODE_NO_RFC9113_WS) ? NGHTTP2_AMD_CHECK_VALUE : NGHTTP2_AMD_CHECK_VALUE_RFC9113)) != 0;
 }
-inline bool disallowed(int32_t token) {
+HDHTTP_FN bool disallowed(int32_t token) {
   return token == kTokConnection || token == kTokKeepAlive || token == kTokProxyConnection ||
          token == kTokTransferEncoding || token == kTokUpgrade;
 }
 
-inline int request_on_header(State *st, uint32_t mode, const Field &f) {  // :188-334
+HDHTTP_FN int request_on_header(State *st, uint32_t mode, const Field &f) {  // :188-334
   const int kErr = NGHTTP2_AMD_ERR_HTTP_HEADER, kIgn = NGHTTP2_AMD_ERR_IGN_HTTP_HEADER;
   switch (f.token) {
   case kTok_Authority:
@@ -243,13 +248,13 @@ inline int request_on_header(State *st, uint32_t mode, const Field &f) {  // :18
     // (the structured value's parse, :308-321, is the caller's)
     break;
   default:
-    if (f.name[0] == ':') return kErr;
+    if (first_byte(f) == ':') return kErr;
     if (!check_header_value(mode, f)) return kIgn;
   }
   return 0;
 }
 
-inline int response_on_header(State *st, uint32_t mode, const Field &f) {  // :336-403
+HDHTTP_FN int response_on_header(State *st, uint32_t mode, const Field &f) {  // :336-403
   const int kErr = NGHTTP2_AMD_ERR_HTTP_HEADER;
   const bool uint_ok = (f.facts & NGHTTP2_AMD_HTTP_FACT_UINT) != 0;
   switch (f.token) {
@@ -283,18 +288,21 @@ inline int response_on_header(State *st, uint32_t mode, const Field &f) {  // :3
     if (!(f.facts & NGHTTP2_AMD_HTTP_FACT_TE_TRAILERS)) return kErr;
     break;
   default:
-    if (f.name[0] == ':') return kErr;
+    if (first_byte(f) == ':') return kErr;
     if (!check_header_value(mode, f)) return NGHTTP2_AMD_ERR_IGN_HTTP_HEADER;
   }
   return 0;
 }
 
-inline int on_header(State *st, uint32_t mode, const Field &f) {  // :405-447
+// `cls` is hdcls::kTable's bytes where the caller runs: a kernel passes its
+// device copy (the name loop below indexes it)
+HDHTTP_FN int on_header(State *st, uint32_t mode, const Field &f,
+                        const uint8_t *cls = hdcls::kTable.cls) {  // :405-447
   if (f.name_len == 0) {
     st->http_flags |= NGHTTP2_AMD_HTTP_FLAG_PSEUDO_HEADER_DISALLOWED;
     return NGHTTP2_AMD_ERR_IGN_HTTP_HEADER;
   }
-  if (f.name[0] == ':') {
+  if (first_byte(f) == ':') {
     if (f.token == -1 || (mode & NGHTTP2_AMD_HTTP_MODE_TRAILER) ||
         (st->http_flags & NGHTTP2_AMD_HTTP_FLAG_PSEUDO_HEADER_DISALLOWED))
       return NGHTTP2_AMD_ERR_HTTP_HEADER;
@@ -304,7 +312,7 @@ inline int on_header(State *st, uint32_t mode, const Field &f) {  // :405-447
       // nghttp2_check_nonempty_header_name's first refused byte: an
       // upper-case letter is 2 (a stream error), any other 0 (ignored)
       for (size_t i = 0; i < f.name_len; ++i)
-        if (hdcls::kTable.cls[f.name[i]] & hdcls::kBadName)
+        if (cls[f.name[i]] & hdcls::kBadName)
           return hdcls::is_upper(f.name[i]) ? NGHTTP2_AMD_ERR_HTTP_HEADER : NGHTTP2_AMD_ERR_IGN_HTTP_HEADER;
     }
   }
@@ -312,14 +320,14 @@ inline int on_header(State *st, uint32_t mode, const Field &f) {  // :405-447
   return response_on_header(st, mode, f);
 }
 
-inline bool check_path(const State *st) {  // :111-116
+HDHTTP_FN bool check_path(const State *st) {  // :111-116
   return (st->http_flags & NGHTTP2_AMD_HTTP_FLAG_SCHEME_HTTP) == 0 ||
          ((st->http_flags & NGHTTP2_AMD_HTTP_FLAG_PATH_REGULAR) ||
           ((st->http_flags & NGHTTP2_AMD_HTTP_FLAG_METH_OPTIONS) &&
            (st->http_flags & NGHTTP2_AMD_HTTP_FLAG_PATH_ASTERISK)));
 }
 
-inline int on_request_headers(State *st, uint32_t mode) {  // :449-484
+HDHTTP_FN int on_request_headers(State *st, uint32_t mode) {  // :449-484
   const uint32_t fl = st->http_flags;
   if (!(fl & NGHTTP2_AMD_HTTP_FLAG__PROTOCOL) && (fl & NGHTTP2_AMD_HTTP_FLAG_METH_CONNECT)) {
     if ((fl & (NGHTTP2_AMD_HTTP_FLAG__SCHEME | NGHTTP2_AMD_HTTP_FLAG__PATH)) ||
@@ -342,7 +350,7 @@ inline int on_request_headers(State *st, uint32_t mode) {  // :449-484
   return 0;
 }
 
-inline int on_response_headers(State *st) {  // :486-511
+HDHTTP_FN int on_response_headers(State *st) {  // :486-511
   if ((st->http_flags & NGHTTP2_AMD_HTTP_FLAG__STATUS) == 0) return -1;
   if (st->status_code / 100 == 1) {  // non-final response
     st->http_flags = (st->http_flags & NGHTTP2_AMD_HTTP_FLAG_METH_ALL) | NGHTTP2_AMD_HTTP_FLAG_EXPECT_FINAL_RESPONSE;

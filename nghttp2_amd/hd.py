@@ -861,6 +861,11 @@ def _replay_lib():
         L.nghttp2_amd_hd_dev_inflate_workspace_size.restype = sz
         L.nghttp2_amd_hd_dev_inflate_blocks.argtypes = [vp, vp, sz, vp, u32, vp, vp, sz, vp, vp, vp, sz, vp, vp,
                                                         u32, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
+        L.nghttp2_amd_hd_dev_fields_http_workspace_size.argtypes = [sz, u32]
+        L.nghttp2_amd_hd_dev_fields_http_workspace_size.restype = sz
+        L.nghttp2_amd_hd_dev_fields_http.argtypes = [vp, sz, vp, sz, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, sz,
+                                                     vp]
+        L.nghttp2_amd_hd_dev_fields_http_totals.argtypes = [vp, vp, vp]
         L.nghttp2_amd_hd_replay_host_init.argtypes = [vp]
         L.nghttp2_amd_hd_replay_host_init.restype = None
         L.nghttp2_amd_hd_replay_host_change_table_size.argtypes = [vp, vp, u32, u32]
@@ -885,6 +890,24 @@ def replay_fields(nva, arena, block_nv_off, out_status):
                                           nv["value_off"].tolist(), nv["value_len"].tolist(),
                                           nv["flags"].tolist())]
     return status, [flat[off[i]:off[i + 1]] for i in range(len(status))]
+
+
+def replay_annotated(r):
+    """A ReplayedBlocks of a call with checks, tokens or http, read back
+    (synchronises) in inflate_blocks' result order: (status, fields), then the
+    (nfields, 2) masks, the tokens, and the verdicts, the states after the
+    blocks (a structured array) and the list of the blocks' results, each
+    where the call was asked for it."""
+    res = replay_fields(r.nva, r.arena, r.block_nv_off, r.status)
+    nf = int(r.block_nv_off[-1].item()) & 0xFFFFFFFF
+    if r.checks is not None:
+        res += (r.checks.cpu().numpy()[:2 * nf].reshape(-1, 2),)
+    if r.tokens is not None:
+        res += (r.tokens.cpu().numpy()[:nf],)
+    if r.block_http is not None:
+        res += (r.verdicts.cpu().numpy()[:nf], r.http_state.cpu().numpy().view(_HTTP_STATE_DTYPE),
+                r.block_http.cpu().tolist())
+    return res
 
 
 def _conn_state(hdr, entries, raw):
@@ -982,7 +1005,16 @@ class HostReplayInflater:
 # is uint8 [24 * nva_cap] (nghttp2_amd_hd_nv records), arena uint8, block_nv_off
 # int32[n+1] holding uint32, status int32[n], totals int32[4] = {fields, arena
 # bytes, DEV_OVERFLOW_* bits, 0}.  replay_fields(*r[:4]) gives the fields.
-ReplayedBlocks = collections.namedtuple("ReplayedBlocks", "nva arena block_nv_off status totals")
+# A call with checks, tokens or http (nghttp2_amd_hd_dev_fields_http behind the
+# replay) also leaves checks uint8 [2 * nva_cap], tokens int32 [nva_cap],
+# verdicts int32 [nva_cap], http_state uint8 [16 * n] (_HTTP_STATE_DTYPE
+# records) and block_http int32 [n]; None where not asked for.  Of the per-field
+# arrays the first totals[0] entries are written.  replay_annotated(r) reads
+# them back.
+ReplayedBlocks = collections.namedtuple(
+    "ReplayedBlocks", "nva arena block_nv_off status totals checks tokens verdicts http_state block_http",
+    defaults=(None,) * 5)
+DEV_FIELDS_NOT_REPLAYED, DEV_FIELDS_ARENA_SHORT = 0x1, 0x2
 
 
 class DeviceInflaters:
@@ -999,7 +1031,7 @@ class DeviceInflaters:
         self.device = torch.device(device if device is not None else "cuda")
         self.L = _replay_lib()
         self.nconn, self.table_bytes = int(nconn), int(table_bytes)
-        self._ws = None
+        self._ws = self._fields_ws = None
         p = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _check(self.L.nghttp2_amd_hd_dev_inflaters_new(ctypes.byref(p), self.nconn, self.table_bytes,
@@ -1072,13 +1104,67 @@ class DeviceInflaters:
         np.cumsum(np.bincount(conn, minlength=self.nconn), out=off[1:])
         return self._dev(off, np.uint32), self._dev(order if len(order) else [0], np.uint32)
 
+    def fields_totals(self, stream=None):
+        """The totals word of the last call with checks, tokens or http
+        (synchronises the stream): [fields examined, their arena bytes,
+        DEV_FIELDS_* bits, 0]."""
+        t = np.zeros(4, np.uint32)
+        if self._fields_ws is not None:
+            _check(self.L.nghttp2_amd_hd_dev_fields_http_totals(_p(self._fields_ws), t.ctypes.data, _stream(stream)),
+                   "dev_fields_http_totals")
+        return t.tolist()
+
+    def _annotate(self, r, nva_cap, n, checks, tokens, http, http_state, s):
+        """nghttp2_amd_hd_dev_fields_http behind a replay, on stream s."""
+        torch = self.torch
+        need = self.L.nghttp2_amd_hd_dev_fields_http_workspace_size(nva_cap, n)
+        chk = tok = modes = states = verd = bhttp = None
+        with torch.cuda.stream(s):
+            if self._fields_ws is None or self._fields_ws.numel() < need:
+                self._fields_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if checks:
+                chk = torch.empty(2 * max(1, nva_cap), dtype=torch.uint8, device=self.device)
+            if tokens:
+                tok = torch.empty(max(1, nva_cap), dtype=torch.int32, device=self.device)
+            if http is not None:
+                if hasattr(http, "device"):
+                    modes = http.to(device=self.device, dtype=torch.uint8)
+                else:
+                    modes = torch.from_numpy(np.fromiter((int(m) for m in http), np.uint8, count=n)).to(self.device)
+                if modes.numel() != n:
+                    raise ValueError("http: one mode per block")
+                if http_state is None:  # fresh streams: {0, -1, -1}
+                    states = torch.full((n, 4), -1, dtype=torch.int32, device=self.device)
+                    states[:, 0] = 0
+                    states = states.view(torch.uint8).reshape(-1)
+                else:  # (a copy: the caller's states stay as they are)
+                    states = http_state.to(self.device).contiguous().view(torch.uint8).reshape(-1).clone()
+                if states.numel() != n * _HTTP_STATE_DTYPE.itemsize:
+                    raise ValueError("http_state: one 16-byte state per block")
+                verd = torch.empty(max(1, nva_cap), dtype=torch.int32, device=self.device)
+                bhttp = torch.empty(n, dtype=torch.int32, device=self.device)
+        rv = self.L.nghttp2_amd_hd_dev_fields_http(
+            _p(r.nva), nva_cap, _p(r.arena), r.arena.untyped_storage().nbytes(), _p(r.block_nv_off), _p(r.status),
+            _p(r.totals), n, _p(chk), _p(tok), _p(modes), _p(states), _p(verd), _p(bhttp), _p(self._fields_ws),
+            self._fields_ws.numel(), ctypes.c_void_p(s.cuda_stream))
+        _check(rv, "dev_fields_http")
+        return r._replace(checks=chk, tokens=tok, verdicts=verd, http_state=states, block_http=bhttp)
+
     def inflate_parsed(self, wire, block_off, parsed, dst, dst_off, status, conn_blk_off, conn_blk,
-                       nva_cap=None, arena_cap=None, stream=None):
+                       nva_cap=None, arena_cap=None, stream=None, checks=False, tokens=False, http=None,
+                       http_state=None):
         """nghttp2_amd_hd_dev_inflate_blocks on tensors: the parse's results
         (a ParsedBlocks), the decode's (dst, dst_off, status; None for a batch
         without Huffman literals) and the CSR of csr().  nva_cap defaults to
         the parse's ops_cap, which cannot overflow.  Nothing is read back:
-        returns a ReplayedBlocks."""
+        returns a ReplayedBlocks.
+        checks, tokens, http and http_state are inflate_blocks' and queue
+        nghttp2_amd_hd_dev_fields_http behind the replay: http is a device
+        uint8 tensor or a host sequence of HTTP_MODE_* values, one per block,
+        http_state a device tensor of 16-byte _HTTP_STATE_DTYPE records (any
+        dtype; it is copied, not changed) or None for fresh streams.  A host
+        sequence is uploaded, which waits for the stream.  The arena is
+        allocated with the slack the batch kernels' pool rule asks for."""
         torch = self.torch
         n = block_off.numel() - 1
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
@@ -1090,7 +1176,8 @@ class DeviceInflaters:
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             nva = torch.empty(max(1, nva_cap) * _NV_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-            arena = torch.empty(max(1, arena_cap), dtype=torch.uint8, device=self.device)
+            # (readable to align_up(arena bytes, 16) + 16: the pool rule)
+            arena = torch.empty((max(1, arena_cap) + 15) // 16 * 16 + 16, dtype=torch.uint8, device=self.device)
             nv_off = torch.zeros(n + 1, dtype=torch.int32, device=self.device)
             out_status = torch.empty(max(1, n), dtype=torch.int32, device=self.device)
             totals = torch.zeros(4, dtype=torch.int32, device=self.device)
@@ -1106,10 +1193,13 @@ class DeviceInflaters:
             _p(conn_blk_off), _p(conn_blk), _p(nva), nva_cap, _p(arena), arena_cap, _p(nv_off), _p(out_status),
             _p(totals), _p(self._ws), self._ws.numel(), ctypes.c_void_p(s.cuda_stream))
         _check(rv, "dev_inflate_blocks")
-        return ReplayedBlocks(nva, arena[:arena_cap], nv_off, out_status[:n], totals)
+        r = ReplayedBlocks(nva, arena[:arena_cap], nv_off, out_status[:n], totals)
+        if checks or tokens or http is not None:
+            r = self._annotate(r, nva_cap, n, checks, tokens, http, http_state, s)
+        return r
 
     def inflate(self, codec, wire, block_off, conn_of_block, wire_bytes=None, nlits=None, enc_bytes=None,
-                arena_cap=None, stream=None, csr=None):
+                arena_cap=None, stream=None, csr=None, checks=False, tokens=False, http=None, http_state=None):
         """parse -> gather -> decode_auto -> replay of a batch on the device:
         block i is wire[block_off[i]:block_off[i+1]] and belongs to
         connection conn_of_block[i] (a host sequence).  Returns a
@@ -1125,7 +1215,10 @@ class DeviceInflaters:
         no host synchronisation between them.  Without an arena_cap the call starts from four times the wire,
         reads out_totals and repeats the replay with the reported need when
         the arena was too small; with one, nothing is read and an overflow
-        is the caller's to see in totals[2]."""
+        is the caller's to see in totals[2].
+        checks, tokens, http and http_state: see inflate_parsed; the repeated
+        replay repeats them (an overflowed call wrote none and changed no
+        state)."""
         torch = self.torch
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         off, blk = csr if csr is not None else self.csr(conn_of_block)
@@ -1142,14 +1235,15 @@ class DeviceInflaters:
         dec = (None, None, None)
         if nlits:
             dec = codec.decode_auto(pool, lit_off[:nlits + 1], enc_bytes=enc_bytes, stream=s)
+        ann = dict(checks=checks, tokens=tokens, http=http, http_state=http_state)
         r = self.inflate_parsed(wire, block_off, pb, dec[0], dec[1], dec[2], off, blk, arena_cap=arena_cap,
-                                stream=s)
+                                stream=s, **ann)
         if arena_cap is None:
             with torch.cuda.stream(s):
                 t = r.totals.cpu().numpy().view(np.uint32)
             if t[2] & DEV_OVERFLOW_ARENA and not t[2] & DEV_OVERFLOW_U32:
                 r = self.inflate_parsed(wire, block_off, pb, dec[0], dec[1], dec[2], off, blk,
-                                        arena_cap=int(t[1]), stream=s)
+                                        arena_cap=int(t[1]), stream=s, **ann)
         return r
 
 

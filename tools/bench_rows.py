@@ -1058,6 +1058,178 @@ def bench_dev_inflate(nconn=256, per_conn=8, fields=16, runs=5, steps=20):
                     "nghttp2_amd_hd_inflate_blocks on the same blocks from host memory, wall time"}
 
 
+def bench_dev_inflate_http(nconn=256, per_conn=8, fields=16, runs=5, steps=20):
+    """bench_dev_inflate's batch and method with the annotations: the device
+    chain with nghttp2_amd_hd_dev_fields_http at its end (masks, tokens,
+    verdicts, states and block results, every block a request on a fresh
+    stream) against nghttp2_amd_hd_inflate_blocks_http on the same blocks
+    from host memory, and the chain without the new call as the parent has
+    it.  The three alternate call by call, fresh contexts each run.  The new
+    call runs with nva_cap = the parse's bound, as the replay does, and
+    (chain_http_tight) with nva_cap = the batch's field count."""
+    import ctypes
+    import statistics
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    blocks, conns = make_blocks(nconn, per_conn, fields)
+    m = len(blocks)
+    wire = b"".join(blocks)
+    W = len(wire)
+    off = np.cumsum([0] + [len(b) for b in blocks]).astype(np.uint32)
+    dev = torch.device("cuda:0")
+    codec = nghttp2_amd.HuffmanBatchCodec(dev)
+    L = hd._replay_lib()
+    tw = torch.from_numpy(np.frombuffer(bytearray(wire), np.uint8)).to(dev)
+    to = torch.from_numpy(off.view(np.int32)).to(dev)
+    modes = [hd.HTTP_MODE_REQUEST] * m
+    # the batch's sizes and the results to hold the timed calls to: the host call's
+    first = nghttp2_amd.DeviceInflaters(nconn, 4096)
+    want = hd.replay_annotated(first.inflate(codec, tw, to, conns, checks=True, tokens=True, http=modes))
+    host = nghttp2_amd.inflate_blocks(_fresh_for(conns, nconn), blocks, checks=True, tokens=True, http=modes)
+    assert want[:2] == host[:2] and want[6] == host[6]
+    assert all(a.tolist() == b.tolist() for a, b in zip(want[2:6], host[2:6]))
+    nfields = len(host[3])
+    nbytes = sum(len(n) + len(v) + 2 for fs in host[1] for n, v, _ in fs)
+    ops_cap, lits_cap, pool_cap, ws_bytes = hd.parse_blocks_bound(W, m)
+    i32, u8 = torch.int32, torch.uint8
+    ops = torch.empty((ops_cap, 8), dtype=i32, device=dev)
+    op_off, lit_base = torch.empty(m + 1, dtype=i32, device=dev), torch.empty(m + 1, dtype=i32, device=dev)
+    status, totals = torch.empty(m, dtype=i32, device=dev), torch.empty(4, dtype=i32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=u8, device=dev)
+    lit_off = torch.empty(lits_cap + 1, dtype=i32, device=dev)
+    pool = torch.empty(pool_cap, dtype=u8, device=dev)
+    st = hd._stream(None)
+    p = hd._p
+    L.nghttp2_amd_hd_parse_blocks_batch(p(tw), p(to), m, p(op_off), p(ops), ops_cap, p(status), p(lit_base), p(totals),
+                                        p(ws), ws_bytes, st)
+    tot = [int(x) for x in totals.cpu().numpy().view(np.uint32)]
+    T, E = tot[1], tot[2]
+    dst = torch.empty(codec.decode_bound(E, T), dtype=u8, device=dev)
+    dst_off, dstatus = torch.empty(T + 1, dtype=i32, device=dev), torch.empty(T, dtype=i32, device=dev)
+    nva = torch.empty(24 * ops_cap, dtype=u8, device=dev)
+    arena_bytes = (nbytes + 15) // 16 * 16 + 16  # the pool rule
+    arena = torch.empty(arena_bytes, dtype=u8, device=dev)
+    nv_off, out_status = torch.empty(m + 1, dtype=i32, device=dev), torch.empty(m, dtype=i32, device=dev)
+    out_totals = torch.empty(4, dtype=i32, device=dev)
+    csr_off, csr_blk = first.csr(conns)
+    rws = torch.empty(L.nghttp2_amd_hd_dev_inflate_workspace_size(nconn, 4096, ops_cap, m), dtype=u8, device=dev)
+    fws = torch.empty(L.nghttp2_amd_hd_dev_fields_http_workspace_size(ops_cap, m), dtype=u8, device=dev)
+    chk = torch.empty(2 * ops_cap, dtype=u8, device=dev)
+    tok, verd = torch.empty(ops_cap, dtype=i32, device=dev), torch.empty(ops_cap, dtype=i32, device=dev)
+    dmodes = torch.from_numpy(np.array(modes, np.uint8)).to(dev)
+    fresh = torch.from_numpy(np.array([(0, -1, -1)] * m, hd._HTTP_STATE_DTYPE).view(np.uint8).copy()).to(dev)
+    dstate, bhttp = fresh.clone(), torch.empty(m, dtype=i32, device=dev)
+    cur = {}
+
+    def chain():
+        rv = L.nghttp2_amd_hd_parse_blocks_batch(p(tw), p(to), m, p(op_off), p(ops), ops_cap, p(status), p(lit_base),
+                                                 p(totals), p(ws), ws_bytes, st)
+        rv |= L.nghttp2_amd_hd_gather_literals_batch(p(tw), W, p(ops), ops_cap, p(totals), p(lit_off), lits_cap,
+                                                     p(pool), pool_cap, st)
+        rv |= L.nghttp2_amd_hd_huff_decode_batch_auto(p(pool), p(lit_off), T, E, p(dst), dst.numel(), p(dst_off),
+                                                      p(dstatus), None, None, st)
+        rv |= L.nghttp2_amd_hd_dev_inflate_blocks(
+            cur["set"].p, p(tw), W, p(to), m, p(op_off), p(ops), ops_cap, p(status), p(totals), p(dst), dst.numel(),
+            p(dst_off), p(dstatus), T, p(csr_off), p(csr_blk), p(nva), ops_cap, p(arena), nbytes, p(nv_off),
+            p(out_status), p(out_totals), p(rws), rws.numel(), st)
+        assert rv == 0
+
+    def chain_http(cap=ops_cap):
+        chain()
+        dstate.copy_(fresh)  # (the streams' states are the call's input: fresh ones each time)
+        rv = L.nghttp2_amd_hd_dev_fields_http(p(nva), cap, p(arena), arena_bytes, p(nv_off), p(out_status),
+                                              p(out_totals), m, p(chk), p(tok), p(dmodes), p(dstate), p(verd),
+                                              p(bhttp), p(fws), fws.numel(), st)
+        assert rv == 0
+
+    LI = hd._inflate_lib()
+    keep = [ctypes.create_string_buffer(b, len(b)) for b in blocks]
+    ptrs = (ctypes.c_void_p * m)(*[ctypes.cast(k, ctypes.c_void_p) for k in keep])
+    lens = (ctypes.c_size_t * m)(*[len(b) for b in blocks])
+    hnva_cap, harena_cap = W + 16, 8 * W + 4096
+    hnva = (hd._Nv * hnva_cap)()
+    harena = (ctypes.c_uint8 * harena_cap)()
+    stc, hbhttp = (ctypes.c_int32 * m)(), (ctypes.c_int32 * m)()
+    hchk = (ctypes.c_uint8 * (2 * hnva_cap))()
+    htok, hverd = (ctypes.c_int32 * hnva_cap)(), (ctypes.c_int32 * hnva_cap)()
+    hmodes = (ctypes.c_uint8 * m)(*modes)
+    hfresh = np.array([(0, -1, -1)] * m, hd._HTTP_STATE_DTYPE)
+    hstate = hfresh.copy()
+    nv_used, ar_used = ctypes.c_size_t(), ctypes.c_size_t()
+
+    def inflate_http():
+        t0 = time.perf_counter()
+        hstate[:] = hfresh
+        rv = LI.nghttp2_amd_hd_inflate_blocks_http(cur["ip"], m, ptrs, lens, hnva, hnva_cap, ctypes.byref(nv_used),
+                                                   harena, harena_cap, ctypes.byref(ar_used), stc, hchk, htok, hmodes,
+                                                   ctypes.c_void_p(hstate.ctypes.data), hverd, hbhttp, st)
+        assert rv == 0
+        return (time.perf_counter() - t0) * 1e6
+
+    def tight():
+        chain_http(nfields)
+
+    forms = {"chain": chain, "chain_http": chain_http, "chain_http_tight": tight}
+    s = torch.cuda.current_stream()
+    per_run = []
+    for _ in range(runs):
+        cur["set"] = nghttp2_amd.DeviceInflaters(nconn, 4096)
+        cur["infs"] = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
+        cur["ip"] = (ctypes.c_void_p * m)(*[cur["infs"][c].p.value for c in conns])
+        for _ in range(3):
+            for f in forms.values():
+                f()
+            inflate_http()
+        ev, hostt, wall = {k: [] for k in forms}, [], {k: [] for k in forms}
+        for _ in range(steps):
+            for k, f in forms.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(s)
+                f()
+                b.record(s)
+                ev[k].append((a, b))
+            hostt.append(inflate_http())
+        torch.cuda.synchronize()
+        for _ in range(steps):
+            for k, f in forms.items():
+                s.synchronize()
+                t0 = time.perf_counter()
+                f()
+                s.synchronize()
+                wall[k].append((time.perf_counter() - t0) * 1e6)
+            inflate_http()
+        r = {"inflate_http_call_us_median": round(statistics.median(hostt), 1)}
+        for k in forms:
+            t = [a.elapsed_time(b) * 1e3 for a, b in ev[k]]
+            r[k + "_us_best"] = round(min(t), 2)
+            r[k + "_us_median"] = round(float(np.median(t)), 2)
+            r[k + "_wall_us_median"] = round(statistics.median(wall[k]), 1)
+        per_run.append(r)
+    # the timed calls' last results are the batch's, and the host's
+    chain_http()
+    torch.cuda.synchronize()
+    assert hd.replay_fields(nva, arena[:nbytes], nv_off, out_status) == tuple(host[:2])
+    assert chk.cpu().numpy()[:2 * nfields].reshape(-1, 2).tolist() == host[2].tolist()
+    assert tok.cpu().numpy()[:nfields].tolist() == host[3].tolist()
+    assert verd.cpu().numpy()[:nfields].tolist() == host[4].tolist()
+    assert dstate.cpu().numpy().view(hd._HTTP_STATE_DTYPE).tolist() == host[5].tolist() == hstate.tolist()
+    assert bhttp.cpu().tolist() == host[6] == list(hbhttp)
+    spread = {}
+    for k in [k for k in per_run[0] if k.endswith("_median")]:
+        v = [r[k] for r in per_run]
+        spread[k] = {"median": round(statistics.median(v), 1), "min": min(v), "max": max(v)}
+    return {"blocks": m, "connections": nconn, "wire_bytes": W, "ops": tot[0], "huffman_literals": T,
+            "huffman_bytes": E, "fields": nfields, "arena_bytes": nbytes, "nva_cap": ops_cap, "runs": runs,
+            "steps": steps, "over_runs": spread, "per_run": per_run,
+            "note": "chain: parse + gather + decode_batch_auto + dev_inflate_blocks as in the dev_inflate row; "
+                    "chain_http: the same followed by nghttp2_amd_hd_dev_fields_http (all five outputs, a copy of "
+                    "the fresh states in front) with nva_cap = the parse's bound; chain_http_tight: with nva_cap = "
+                    "the batch's fields; HIP events around the calls (_us_*) and wall time around the calls and one "
+                    "stream synchronisation (_wall_us_median); inflate_http_call: "
+                    "nghttp2_amd_hd_inflate_blocks_http on the same blocks from host memory, wall time"}
+
+
 def _fresh_for(conns, nconn):
     import nghttp2_amd
     infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
@@ -1079,5 +1251,6 @@ if __name__ == "__main__":
            "inflate_http": bench_inflate_http,
            "parse": bench_parse,
            "dev_inflate": bench_dev_inflate,
+           "dev_inflate_http": bench_dev_inflate_http,
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
