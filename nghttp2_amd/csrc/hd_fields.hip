@@ -23,8 +23,8 @@
 //                    slots below the field count go to the caller's arrays
 //   k_http_facts     (hd_http.hip, unchanged) on the values
 //   k_http_blocks    one lane per block, 64 blocks per one-wave workgroup: the
-//                    lane runs hdhttp::on_header over its block's fields in
-//                    order and the block-end function behind them.
+//                    lane runs its block's fields in order through
+//                    hdhttp::BlockRun, the host inflater's driver.
 // The three batch kernels write every slot they are launched for, the slots
 // past the count included (INVALID), so they write into the workspace and
 // k_field_publish copies what the caller may see.
@@ -64,25 +64,19 @@ struct Ws {
 };
 __host__ Ws ws_layout(void *base, size_t cap) {
   Ws w;
-  uint8_t *p = (uint8_t *)base;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t *q = p + at;
-    at += hdhost::round16(bytes);
-    return q;
-  };
-  w.totals = (uint32_t *)take(4 * sizeof(uint32_t));
-  w.all_off = (uint32_t *)take((2 * cap + 1) * sizeof(uint32_t));
-  w.all_len = (int32_t *)take(2 * cap * sizeof(int32_t));
-  w.name_off = (uint32_t *)take((cap + 1) * sizeof(uint32_t));
-  w.name_len = (int32_t *)take(cap * sizeof(int32_t));
-  w.value_off = (uint32_t *)take((cap + 1) * sizeof(uint32_t));
-  w.value_len = (int32_t *)take(cap * sizeof(int32_t));
-  w.numbers = (int64_t *)take(cap * sizeof(int64_t));
-  w.facts = (uint32_t *)take(cap * sizeof(uint32_t));
-  w.tokens = (int32_t *)take(cap * sizeof(int32_t));
-  w.masks = take(2 * cap);
-  w.total = at;
+  hdhost::Carve c{base};
+  w.totals = c.take<uint32_t>(4);
+  w.all_off = c.take<uint32_t>(2 * cap + 1);
+  w.all_len = c.take<int32_t>(2 * cap);
+  w.name_off = c.take<uint32_t>(cap + 1);
+  w.name_len = c.take<int32_t>(cap);
+  w.value_off = c.take<uint32_t>(cap + 1);
+  w.value_len = c.take<int32_t>(cap);
+  w.numbers = c.take<int64_t>(cap);
+  w.facts = c.take<uint32_t>(cap);
+  w.tokens = c.take<int32_t>(cap);
+  w.masks = c.take<uint8_t>(2 * cap);
+  w.total = c.total();
   return w;
 }
 
@@ -182,7 +176,7 @@ __global__ __launch_bounds__(HB_WG) void k_http_blocks(
   uint32_t f0 = block_nv_off[i], f1 = block_nv_off[i + 1];
   const uint32_t mode = block_modes[i];
   const int32_t status = out_status[i];
-  hdhttp::State st = block_state[i];
+  hdhttp::BlockRun run = {block_state[i], mode};
   if (skip) return;  // no field was written, or none may be read: nothing changes
   f0 = min(f0, nf);
   f1 = max(min(f1, nf), f0);
@@ -197,7 +191,6 @@ __global__ __launch_bounds__(HB_WG) void k_http_blocks(
   if (f0 + 1u < f1) r1 = load_rec(nva, masks, tokens, facts, numbers, f0 + 1u);
   fit(r0);
   if (r0.name_len) b0 = arena[r0.name_off];
-  int32_t result = 0;
   uint32_t k = f0;
   for (; k < f1; ++k) {
     Rec r2 = none;
@@ -208,29 +201,19 @@ __global__ __launch_bounds__(HB_WG) void k_http_blocks(
     if (r1.name_len) b1 = arena[r1.name_off];
     const hdhttp::Field f = {arena + r0.name_off, r0.name_len,       r0.value_len, r0.token, r0.masks & 0xFFu,
                              r0.masks >> 8,       r0.facts,          r0.number,    (int32_t)b0};
-    const int rv = hdhttp::on_header(&st, mode, f, kNameTable.cls);
+    const int rv = run.step(f, kNameTable.cls);
     if (nv_verdicts) nv_verdicts[k] = rv;
-    if (rv == NGHTTP2_AMD_ERR_HTTP_HEADER) {
-      result = rv;
-      break;
-    }
+    if (run.stopped) break;
     r0 = r1;
     b0 = b1;
     r1 = r2;
   }
-  // behind the block's first stream error: not examined, the state as it is
-  const bool stopped = k < f1;
+  // behind the block's first stream error a step answers NOT_EXAMINED: stored, not asked for
   if (nv_verdicts)
     for (++k; k < f1; ++k) nv_verdicts[k] = NGHTTP2_AMD_HTTP_NOT_EXAMINED;
-  if (status < 0) {
-    result = status;  // the wire failed (or the store's capacity): no block end
-  } else if (!stopped && !(mode & NGHTTP2_AMD_HTTP_MODE_TRAILER)) {
-    const int rv = (mode & NGHTTP2_AMD_HTTP_MODE_REQUEST) ? hdhttp::on_request_headers(&st, mode)
-                                                          : hdhttp::on_response_headers(&st);
-    if (rv) result = NGHTTP2_AMD_ERR_HTTP_MESSAGING;
-  }
-  block_state[i] = st;
-  if (block_http) block_http[i] = result;
+  run.finish(status);
+  block_state[i] = run.st;
+  if (block_http) block_http[i] = run.result;
 }
 
 constexpr size_t kMaxSlots = 0x7FFFFFFFu;  // 2 * nva_cap strings are one batch of the check

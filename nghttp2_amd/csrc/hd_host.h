@@ -1,8 +1,8 @@
 // hd_host.h -- what the host layers above the C ABI share (hd_inflate.cpp,
 // hd_deflate.cpp, hd_sharded.cpp): the HPACK static table (hd_static.h), the
-// HIP error reports (hip_rv is the kernel
-// layers' own, the .hip files'), and the growable device and pinned host
-// buffers the layers stage their batches in.
+// HIP error reports (hip_rv is the kernel layers' own, the .hip files'), the
+// workspace carver of the .hip files' layouts, and the growable device and
+// pinned host buffers the layers stage their batches in.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,6 +33,21 @@ inline int hip_rv(hipError_t e) {
   return NGHTTP2_AMD_ERR_FATAL;
 }
 inline size_t round16(size_t x) { return (x + 15u) & ~size_t(15); }
+inline uint32_t clamp32(size_t x) { return x > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)x; }
+// A caller's workspace cut into arrays, one after the other: take<T>(count)
+// is the next one, at the next multiple of `align` (a power of two).  With
+// base = nullptr only the offsets count: total() is what the layout needs,
+// the size the *_workspace_size functions report (part of the ABI).
+struct Carve {
+  void *base;
+  size_t at = 0;
+  template <class T> T *take(size_t count, size_t align = 16) {
+    const size_t from = (at + align - 1u) & ~(align - 1u);
+    at = from + count * sizeof(T);
+    return reinterpret_cast<T *>((uintptr_t)base + from);
+  }
+  size_t total() const { return round16(at); }
+};
 // Buffers that grow and never shrink.  Their owner releases them explicitly: no
 // destructor calls HIP (the engines' singletons outlive the runtime at exit).
 struct Buf {

@@ -11,11 +11,13 @@
 // ones are ORs of four per-byte classes, as the masks are; the comparisons
 // against short literals use the string's first 8 bytes and its length.  The
 // step itself (on_header below) is then a pure function of token, masks,
-// facts and number.
+// facts and number, and BlockRun at the end is the one driver of it: a
+// block's fields in order, the stop at the first stream error, the block end.
 //
-// Shared by the host function (nghttp2_amd_hd_http_facts), the inflater's
-// replay and the GPU kernels (k_http_facts, the class table staged in LDS;
-// k_http_blocks of hd_fields.hip, which runs the step and the block ends).
+// Shared by the host function (nghttp2_amd_hd_http_facts) and the GPU kernel
+// (k_http_facts, the class table staged in LDS) for the facts, and by the
+// inflater's replay (hd_inflate.cpp) and k_http_blocks of hd_fields.hip, which
+// both run a block through BlockRun.
 // Plain C++17, no HIP: included by .cpp and .hip sources alike.
 #ifndef NGHTTP2_AMD_HD_HTTP_H
 #define NGHTTP2_AMD_HD_HTTP_H
@@ -367,6 +369,37 @@ HDHTTP_FN int on_response_headers(State *st) {  // :486-511
     st->content_length = -1;
   return 0;
 }
+
+// One block's fields in order on its stream's state, and the block's end.
+// After the first stream error the reference stops calling
+// nghttp2_http_on_header for the stream (lib/nghttp2_session.c:3643-3664): the
+// later fields are not examined and the state stays.
+struct BlockRun {
+  State st;       // in: before the block; out: after it
+  uint32_t mode;  // NGHTTP2_AMD_HTTP_MODE_*
+  bool stopped = false;
+  int32_t result = 0;  // 0, ERR_HTTP_HEADER, ERR_HTTP_MESSAGING or the wire's failure
+  HDHTTP_FN int step(const Field &f, const uint8_t *cls = hdcls::kTable.cls) {
+    if (stopped) return NGHTTP2_AMD_HTTP_NOT_EXAMINED;
+    const int rv = on_header(&st, mode, f, cls);
+    if (rv == NGHTTP2_AMD_ERR_HTTP_HEADER) {
+      stopped = true;
+      result = rv;
+    }
+    return rv;
+  }
+  // wire_status: the inflater's status of the block.  A failed wire (or the
+  // store's capacity) is the result and there is no block end; a sound one
+  // ends with the block-end function of the mode, but for trailers.
+  HDHTTP_FN void finish(int32_t wire_status) {
+    if (wire_status < 0) {
+      result = wire_status;
+    } else if (!stopped && !(mode & NGHTTP2_AMD_HTTP_MODE_TRAILER)) {
+      const int rv = (mode & NGHTTP2_AMD_HTTP_MODE_REQUEST) ? on_request_headers(&st, mode) : on_response_headers(&st);
+      if (rv) result = NGHTTP2_AMD_ERR_HTTP_MESSAGING;
+    }
+  }
+};
 
 }  // namespace hdhttp
 

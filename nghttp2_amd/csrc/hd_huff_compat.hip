@@ -37,19 +37,15 @@
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "../../include/nghttp2_amd_hd_huffman_compat.h"
+#include "hd_host.h"
 
 extern "C" int nghttp2_bufs_addb(nghttp2_bufs *bufs, uint8_t b) __attribute__((weak));
 
 namespace {
 
-bool hip_ok(hipError_t e) {
-  if (e == hipSuccess) return true;
-  fprintf(stderr, "nghttp2_amd_hd (compat): HIP error %s\n", hipGetErrorString(e));
-  return false;
-}
+bool hip_ok(hipError_t e) { return hdhost::hip_ok(e, "compat", nullptr); }
 
-size_t round16(size_t x) { return (x + 15u) & ~size_t(15); }
-
+using hdhost::round16;
 constexpr size_t kCopyMin = 64u << 10;  // string bytes from which a call copies instead of mapping
 
 // Layout of one call (device buffer and pinned block alike):

@@ -447,33 +447,12 @@ struct DirectSink {
   int32_t count() const { return (int32_t)(nv - nv0); }
 };
 
-// An _http call's view of one block: its mode, the stream's state (in: before
-// the block; out: after it) and the block's result.  After the first stream
-// error the reference stops calling nghttp2_http_on_header for the stream
-// (lib/nghttp2_session.c:3643-3664): the later fields are not examined and
-// the state stays.
-struct HttpRun {
-  uint32_t mode;
-  nghttp2_amd_hd_http_state st;
-  bool stopped = false;
-  int32_t result = 0;
-  int32_t step(const char *n, size_t nl, size_t vl, const Ann &a) {
-    if (stopped) return NGHTTP2_AMD_HTTP_NOT_EXAMINED;
-    const int rv = hdhttp::on_header(&st, mode, hdhttp::Field{(const uint8_t *)n, nl, vl, a.tk, a.cn, a.cv, a.vf, a.vn});
-    if (rv == NGHTTP2_AMD_ERR_HTTP_HEADER) {
-      stopped = true;
-      result = rv;
-    }
-    return rv;
-  }
-  // the end of a block whose wire was sound: the block-end function of the mode
-  void end() {
-    if (stopped || (mode & NGHTTP2_AMD_HTTP_MODE_TRAILER)) return;
-    const int rv = (mode & NGHTTP2_AMD_HTTP_MODE_REQUEST) ? hdhttp::on_request_headers(&st, mode)
-                                                          : hdhttp::on_response_headers(&st);
-    if (rv) result = NGHTTP2_AMD_ERR_HTTP_MESSAGING;
-  }
-};
+// An _http call's view of one block: the driver k_http_blocks runs
+// (hd_http.h), its fields built from the annotations.
+typedef hdhttp::BlockRun HttpRun;
+hdhttp::Field http_field(const char *n, size_t nl, size_t vl, const Ann &a) {
+  return hdhttp::Field{(const uint8_t *)n, nl, vl, a.tk, a.cn, a.cv, a.vf, a.vn};
+}
 
 // want: the annotations every emitted field carries.  http: an _http call
 // (want.http) -- every emitted field with its verdict, the block's state and
@@ -512,7 +491,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
       inf->entry(op.value - 1, &n, &nl, &v, &vl);
       static const Ann kNone;
       const Ann &a = want.any() ? inf->entry_ann(op.value - 1, want) : kNone;
-      out.emit(n, nl, v, vl, 0, a, http ? http->step(n, nl, vl, a) : 0);
+      out.emit(n, nl, v, vl, 0, a, http ? http->step(http_field(n, nl, vl, a)) : 0);
       continue;
     }
     const bool new_name = (op.flags & NGHTTP2_AMD_HD_OP_NEW_NAME) != 0;
@@ -540,7 +519,7 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     Ann a = ls.ann(b.in, new_name ? &name : nullptr, val, want);
     if (name_ann) a.cn = name_ann->cn, a.tk = name_ann->tk;
     const uint8_t flags = (op.flags & NGHTTP2_AMD_HD_OP_NO_INDEX) ? 1u : 0u;  // NGHTTP2_NV_FLAG_NO_INDEX
-    out.emit(n, nl, v, vl, flags, a, http ? http->step(n, nl, vl, a) : 0);
+    out.emit(n, nl, v, vl, flags, a, http ? http->step(http_field(n, nl, vl, a)) : 0);
     if (op.flags & NGHTTP2_AMD_HD_OP_INDEX_REQUIRED)  // the table copies the field just emitted
       inf->add(out.last_name(), nl, out.last_value(), vl, a);
   }
@@ -555,10 +534,10 @@ void replay_block(nghttp2_amd_hd_inflater *inf, const Block &b, const LitSrc &ls
     // :2259-2266); every other failure is in the middle of a representation.
     if (!inf->bad) inf->mid_block = !(inf->expect_size && !b.first_is_size);
     inf->bad = true;
-    if (http) http->result = NGHTTP2_AMD_ERR_HEADER_COMP;
+    if (http) http->finish(NGHTTP2_AMD_ERR_HEADER_COMP);
     out.finish(NGHTTP2_AMD_ERR_HEADER_COMP);  // the fields before the error stay emitted
   } else {
-    if (http) http->end();
+    if (http) http->finish(0);
     out.finish(out.count());
   }
 }
@@ -578,7 +557,7 @@ struct Dest {
   const uint8_t *block_modes;
   nghttp2_amd_hd_http_state *block_state;
   int32_t *block_http;
-  HttpRun run(uint32_t i) const { return HttpRun{block_modes[i], block_state[i]}; }
+  HttpRun run(uint32_t i) const { return HttpRun{block_state[i], block_modes[i]}; }
   void set_http(uint32_t i, const nghttp2_amd_hd_http_state &st, int32_t res) const {
     block_state[i] = st;
     if (block_http) block_http[i] = res;

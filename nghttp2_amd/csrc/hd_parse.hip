@@ -180,8 +180,12 @@ __global__ __launch_bounds__(GL_WG) void k_gather(const uint8_t *__restrict__ wi
   }
 }
 
-size_t ws_need(uint32_t n) { return hdhost::round16(((size_t)n + 1u) * sizeof(uint32_t)); }
-uint32_t clamp32(size_t x) { return x > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)x; }
+size_t ws_need(uint32_t n) {  // the workspace is byte_base[n + 1]
+  hdhost::Carve c{nullptr};
+  c.take<uint32_t>((size_t)n + 1u);
+  return c.total();
+}
+using hdhost::clamp32;
 
 }  // namespace
 

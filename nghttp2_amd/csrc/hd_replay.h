@@ -24,7 +24,10 @@
 // with nold only ever falling.  The persistent state changes in the commit.
 //
 // Shared by the host twin (nghttp2_amd_hd_replay_host) and the GPU kernels
-// (k_replay, one lane per connection; k_change_size).  Plain C++17, no HIP.
+// (k_replay, one lane per connection; k_change_size), and with the walk what
+// both sides do around it (at the end of this file): a block's first_is_size,
+// out_totals, a field's record, the header and descriptors a commit leaves.
+// How bytes are copied is each side's own.  Plain C++17, no HIP.
 #ifndef NGHTTP2_AMD_HD_REPLAY_H
 #define NGHTTP2_AMD_HD_REPLAY_H
 
@@ -271,6 +274,53 @@ HDREPLAY_FN BlockResult walk_block(Table *t, uint32_t block, const nghttp2_amd_h
   for (; k < nops; ++k) sink(k, none);
   r.status = err ? err : (int32_t)r.fields;
   return r;
+}
+
+// Whether block wire[w0, w1) opens with a size update (walk_block's first_is_size).
+HDREPLAY_FN bool block_first_is_size(const uint8_t *wire, uint64_t wire_bytes, uint32_t w0, uint32_t w1) {
+  return w0 < w1 && w0 < wire_bytes && hdparse::first_is_size(wire + w0, w1 - w0);
+}
+
+// A call's out_totals from its fields and arena bytes: a sum past uint32
+// saturates both counts, and any overflow bit means nothing was emitted.
+HDREPLAY_FN bool totals_wide(uint64_t fields, uint64_t bytes) { return ((fields | bytes) >> 32) != 0; }
+HDREPLAY_FN void write_totals(uint64_t fields, uint64_t bytes, uint64_t nva_cap, uint64_t arena_cap,
+                              uint32_t *out_totals) {
+  const bool wide = totals_wide(fields, bytes);
+  out_totals[0] = wide ? 0xFFFFFFFFu : (uint32_t)fields;
+  out_totals[1] = wide ? 0xFFFFFFFFu : (uint32_t)bytes;
+  out_totals[2] = (wide ? NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 : 0u) | (fields > nva_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_NVA : 0u) |
+                  (bytes > arena_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_ARENA : 0u);
+  out_totals[3] = 0u;
+}
+
+// The record of a field whose name, NUL, value, NUL start at arena offset
+// `at`, into *out (all 24 bytes: the padding behind flags is written as zero,
+// which a record returned by value would not promise).
+HDREPLAY_FN void field_nv(const FieldRef &fr, uint32_t at, nghttp2_amd_hd_nv *out) {
+  nghttp2_amd_hd_nv nv = {};
+  nv.block = fr.block;
+  nv.name_off = at;
+  nv.name_len = ref_len(fr.name);
+  nv.value_off = at + nv.name_len + 1u;
+  nv.value_len = ref_len(fr.value);
+  nv.flags = (uint8_t)fr.flags;
+  *out = nv;
+}
+
+// The commit.  The live entries, newest first, go to slots head, head + 1, ...
+// of the ring, their bytes back to back into the store's other buffer: the
+// header it leaves, and the descriptor of an entry whose nl + vl bytes are at
+// `at` of that buffer.
+HDREPLAY_FN Conn committed_conn(const Conn &h, uint32_t nnew, uint32_t nold, uint32_t mask) {
+  Conn c = h;
+  c.head = (h.head - nnew) & mask;
+  c.count = nnew + nold;
+  c.cur = (h.cur & 1u) ^ 1u;
+  return c;
+}
+HDREPLAY_FN Entry committed_entry(uint32_t at, uint32_t nl, uint32_t vl) {
+  return Entry{make_ref(SRC_TABLE, at, nl), make_ref(SRC_TABLE, at + nl, vl)};
 }
 
 }  // namespace hdreplay

@@ -77,21 +77,14 @@ struct Ws {
 };
 __host__ Ws ws_layout(void *base, uint32_t nconn, uint32_t table_bytes, size_t ops_cap, uint32_t n) {
   Ws w;
-  uint8_t *p = (uint8_t *)base;
-  size_t at = 0;
-  w.blk_count = (uint32_t *)(p + at);
-  at += ((size_t)n + 1u) * sizeof(uint32_t);
-  w.blk_bytes = (uint32_t *)(p + at);
-  at += ((size_t)n + 1u) * sizeof(uint32_t);
-  w.clear_bytes = at;
-  at = hdhost::round16(at);
-  w.left = (Left *)(p + at);
-  at += (size_t)nconn * sizeof(Left);
-  w.fresh = (Entry *)(p + at);
-  at += (size_t)nconn * (table_bytes / hdreplay::kOverhead) * sizeof(Entry);
-  w.fref = (FieldRef *)(p + at);
-  at += ops_cap * sizeof(FieldRef);
-  w.total = at;
+  hdhost::Carve c{base};
+  w.blk_count = c.take<uint32_t>((size_t)n + 1u, 4);  // (the two counter arrays are one span: one clear)
+  w.blk_bytes = c.take<uint32_t>((size_t)n + 1u, 4);
+  w.clear_bytes = c.at;
+  w.left = c.take<Left>(nconn);
+  w.fresh = c.take<Entry>((size_t)nconn * (table_bytes / hdreplay::kOverhead));
+  w.fref = c.take<FieldRef>(ops_cap);
+  w.total = c.total();
   return w;
 }
 
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(RP_WG) void k_replay(
     if (b >= n) continue;
     const uint32_t r0 = min(op_off[b], nops), r1 = min(op_off[b + 1], nops);
     const uint32_t w0 = block_off[b], w1 = block_off[b + 1];
-    const bool first_is_size = w0 < w1 && w0 < wire_bytes && hdparse::first_is_size(wire + w0, w1 - w0);
+    const bool first_is_size = hdreplay::block_first_is_size(wire, wire_bytes, w0, w1);
     const hdreplay::BlockResult r =
         hdreplay::walk_block(&t, b, ops + r0, r1 > r0 ? r1 - r0 : 0u, block_status[b] >= 0, first_is_size, lits,
                              &d_static, FrefStore{fref, r0, ops_cap});
@@ -166,14 +159,7 @@ __global__ __launch_bounds__(RP_WG) void k_replay(
     blk_count[b] = r.fields;
     blk_bytes[b] = r.bytes;
   }
-  Left l;
-  l.h = t.h;
-  l.nnew = t.nnew;
-  l.nhead = t.nhead;
-  l.nold = t.nold;
-  l.walked = 1u;
-  l.pad[0] = l.pad[1] = l.pad[2] = l.pad[3] = 0u;
-  left[c] = l;
+  left[c] = Left{t.h, t.nnew, t.nhead, t.nold, 1u, {0u, 0u, 0u, 0u}};
 }
 
 __global__ __launch_bounds__(SC_WG) void k_replay_scan(const uint32_t *__restrict__ totals,
@@ -185,18 +171,11 @@ __global__ __launch_bounds__(SC_WG) void k_replay_scan(const uint32_t *__restric
   hdscan::Share s0, s1;
   const uint64_t t0 = hdscan::scan_sums(blk_count, n, wsum[0], &s0);
   const uint64_t t1 = hdscan::scan_sums(blk_bytes, n, wsum[1], &s1);
-  const bool wide = ((t0 | t1) >> 32) != 0;
-  if (!wide) {
+  if (!hdreplay::totals_wide(t0, t1)) {
     hdscan::scan_write(blk_count, block_nv_off, n, s0, t0);
     hdscan::scan_write(blk_bytes, blk_bytes, n, s1, t1);
   }
-  if (threadIdx.x == 0) {
-    out_totals[0] = wide ? 0xFFFFFFFFu : (uint32_t)t0;
-    out_totals[1] = wide ? 0xFFFFFFFFu : (uint32_t)t1;
-    out_totals[2] = (wide ? NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 : 0u) | (t0 > nva_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_NVA : 0u) |
-                    (t1 > arena_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_ARENA : 0u);
-    out_totals[3] = 0u;
-  }
+  if (threadIdx.x == 0) hdreplay::write_totals(t0, t1, nva_cap, arena_cap, out_totals);
 }
 
 // The four stores a Ref can name, with their sizes: a Ref that reaches past
@@ -269,17 +248,8 @@ __global__ __launch_bounds__(EM_WG) void k_emit(Stores stores, const uint32_t *_
     at = arena_base[fr.block] + fr.before;
     has = has && idx < nva_cap;
   }
-  const uint32_t nl = hdreplay::ref_len(fr.name), vl = hdreplay::ref_len(fr.value);
-  if (has) {
-    nghttp2_amd_hd_nv nv = {};
-    nv.block = fr.block;
-    nv.name_off = at;
-    nv.name_len = nl;
-    nv.value_off = at + nl + 1u;
-    nv.value_len = vl;
-    nv.flags = (uint8_t)fr.flags;
-    nva[idx] = nv;
-  }
+  const uint32_t nl = hdreplay::ref_len(fr.name);
+  if (has) hdreplay::field_nv(fr, at, &nva[idx]);
   wave_copy(stores, has, fr.name, at, arena, arena_cap, true, lane);
   wave_copy(stores, has, fr.value, (uint64_t)at + nl + 1u, arena, arena_cap, true, lane);
 }
@@ -297,11 +267,10 @@ __global__ __launch_bounds__(CM_WG) void k_commit(Stores stores, const uint32_t 
   const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
   Entry *cring = ring + (size_t)c * slots;
   const Entry *cfresh = fresh + (size_t)c * slots;
-  const uint32_t cur = l.h.cur & 1u, other = cur ^ 1u;
-  const uint32_t cur_off = (2u * c + cur) * table_bytes;
-  uint8_t *to = store + (size_t)(2u * c + other) * table_bytes;
-  const uint32_t count = l.nnew + l.nold;
-  const uint32_t head = (l.h.head - l.nnew) & mask;
+  const Conn after = hdreplay::committed_conn(l.h, l.nnew, l.nold, mask);
+  const uint32_t cur_off = (2u * c + (l.h.cur & 1u)) * table_bytes;
+  uint8_t *to = store + (size_t)(2u * c + after.cur) * table_bytes;
+  const uint32_t count = after.count, head = after.head;
   // The slots of the entries that stay, ring[h.head + j], are the slots they
   // end in, head + nnew + j: a lane reads the descriptor it then replaces,
   // and the fresh entries go in front of them, into slots no live entry has.
@@ -332,24 +301,13 @@ __global__ __launch_bounds__(CM_WG) void k_commit(Stores stores, const uint32_t 
     const bool fits = ok && (uint64_t)at + len <= table_bytes;
     wave_copy(stores, fits, e.name, at, to, table_bytes, false, lane);
     wave_copy(stores, fits, e.value, (uint64_t)at + nl, to, table_bytes, false, lane);
-    if (live) {
-      Entry d;
-      d.name = hdreplay::make_ref(hdreplay::SRC_TABLE, at, fits ? nl : 0u);
-      d.value = hdreplay::make_ref(hdreplay::SRC_TABLE, at + (fits ? nl : 0u), fits ? vl : 0u);
-      cring[(head + i) & mask] = d;
-    }
+    if (live) cring[(head + i) & mask] = hdreplay::committed_entry(at, fits ? nl : 0u, fits ? vl : 0u);
     run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
   }
-  if (lane == 0u) {
-    Conn h = l.h;
-    h.head = head;
-    h.count = count;
-    h.cur = other;
-    hdr[c] = h;
-  }
+  if (lane == 0u) hdr[c] = after;
 }
 
-uint32_t clamp32(size_t x) { return x > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)x; }
+using hdhost::clamp32;
 bool table_bytes_ok(uint32_t tb) { return tb >= 4096u && (tb & (tb - 1u)) == 0u; }
 
 }  // namespace
@@ -448,15 +406,9 @@ int nghttp2_amd_hd_dev_inflate_blocks(nghttp2_amd_hd_dev_inflaters *set, const u
   const Ws w = ws_layout(workspace, nconn, tb, cap, n);
   if (ws_bytes < w.total) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   hipStream_t st = (hipStream_t)stream;
-  Stores stores;
-  stores.base[0] = nullptr;  // the kernels' own constant pool
-  stores.bytes[0] = hdhost::kStaticPoolBytes;
-  stores.base[1] = wire;
-  stores.bytes[1] = wire_bytes;
-  stores.base[2] = dst;
-  stores.bytes[2] = dst_bytes;
-  stores.base[3] = set->store;
-  stores.bytes[3] = (uint64_t)nconn * 2u * tb;
+  // (store 0 is the kernels' own constant pool)
+  const Stores stores = {{nullptr, wire, dst, set->store},
+                         {hdhost::kStaticPoolBytes, wire_bytes, dst_bytes, (uint64_t)nconn * 2u * tb}};
   // (a block no connection lists counts no field and no byte)
   hipError_t e = hipMemsetAsync(w.blk_count, 0, w.clear_bytes, st);
   if (e != hipSuccess) return hdhost::hip_rv(e);
@@ -511,7 +463,7 @@ int nghttp2_amd_hd_replay_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, uint8_
   std::vector<uint64_t> base(n);
   for (uint32_t b = 0; b < n; ++b) {
     const uint32_t w0 = block_off[b], w1 = block_off[b + 1];
-    const bool first_is_size = w0 < w1 && w0 < wire_bytes && hdparse::first_is_size(wire + w0, w1 - w0);
+    const bool first_is_size = hdreplay::block_first_is_size(wire, wire_bytes, w0, w1);
     FieldRef *out = fref.data() + (op_off[b] - op_off[0]);
     const hdreplay::BlockResult r =
         hdreplay::walk_block(&t, b, ops + op_off[b], op_off[b + 1] - op_off[b], block_status[b] >= 0, first_is_size,
@@ -523,51 +475,32 @@ int nghttp2_amd_hd_replay_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, uint8_
     bytes += r.bytes;
   }
   block_nv_off[n] = (uint32_t)fields;
-  const bool wide = ((fields | bytes) >> 32) != 0;
-  out_totals[0] = wide ? 0xFFFFFFFFu : (uint32_t)fields;
-  out_totals[1] = wide ? 0xFFFFFFFFu : (uint32_t)bytes;
-  out_totals[2] = (wide ? NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 : 0u) | (fields > nva_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_NVA : 0u) |
-                  (bytes > arena_cap ? NGHTTP2_AMD_HD_DEV_OVERFLOW_ARENA : 0u);
-  out_totals[3] = 0u;
+  hdreplay::write_totals(fields, bytes, nva_cap, arena_cap, out_totals);
   if (out_totals[2]) return 0;  // all or nothing: no field, and the table as it was
   const uint8_t *stores[4] = {hdhost::kStaticPool.bytes, wire, dst, store};
   auto bytes_of = [&](Ref r) { return stores[hdreplay::ref_src(r)] + r.off; };
   for (const FieldRef &fr : fref) {
     if (fr.block == hdreplay::kNoField) continue;
-    const uint32_t nl = hdreplay::ref_len(fr.name), vl = hdreplay::ref_len(fr.value);
-    const uint32_t at = (uint32_t)base[fr.block] + fr.before;
-    nghttp2_amd_hd_nv nv = {};
-    nv.block = fr.block;
-    nv.name_off = at;
-    nv.name_len = nl;
-    nv.value_off = at + nl + 1u;
-    nv.value_len = vl;
-    nv.flags = (uint8_t)fr.flags;
-    nva[block_nv_off[fr.block] + fr.ordinal] = nv;
-    if (nl) memcpy(arena + at, bytes_of(fr.name), nl);
-    arena[at + nl] = 0;
-    if (vl) memcpy(arena + nv.value_off, bytes_of(fr.value), vl);
-    arena[nv.value_off + vl] = 0;
+    nghttp2_amd_hd_nv &nv = nva[block_nv_off[fr.block] + fr.ordinal];
+    hdreplay::field_nv(fr, (uint32_t)base[fr.block] + fr.before, &nv);
+    if (nv.name_len) memcpy(arena + nv.name_off, bytes_of(fr.name), nv.name_len);
+    arena[nv.name_off + nv.name_len] = 0;
+    if (nv.value_len) memcpy(arena + nv.value_off, bytes_of(fr.value), nv.value_len);
+    arena[nv.value_off + nv.value_len] = 0;
   }
   // the commit: the live entries' bytes back to back into the other buffer
-  const uint32_t other = cur ^ 1u, count = t.nnew + t.nold, head = (t.h.head - t.nnew) & mask;
-  uint8_t *to = store + (size_t)other * table_bytes;
+  const Conn after = hdreplay::committed_conn(t.h, t.nnew, t.nold, mask);
+  uint8_t *to = store + (size_t)after.cur * table_bytes;
   uint32_t at = 0;
-  for (uint32_t i = 0; i < count; ++i) {
+  for (uint32_t i = 0; i < after.count; ++i) {
     const Entry e = hdreplay::table_get(t, i);
     const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
     if (nl) memcpy(to + at, bytes_of(e.name), nl);
     if (vl) memcpy(to + at + nl, bytes_of(e.value), vl);
-    Entry d;
-    d.name = hdreplay::make_ref(hdreplay::SRC_TABLE, at, nl);
-    d.value = hdreplay::make_ref(hdreplay::SRC_TABLE, at + nl, vl);
-    ring[(head + i) & mask] = d;
+    ring[(after.head + i) & mask] = hdreplay::committed_entry(at, nl, vl);
     at += nl + vl;
   }
-  *hdr = t.h;
-  hdr->head = head;
-  hdr->count = count;
-  hdr->cur = other;
+  *hdr = after;
   return 0;
 }
 
