@@ -1156,6 +1156,191 @@ NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_replay_host(
     size_t arena_cap, uint32_t *block_nv_off, int32_t *out_status, uint32_t *out_totals);
 
 /* ------------------------------------------------------------------ */
+/* Device-resident deflaters: header lists to wire on the GPU             */
+/* ------------------------------------------------------------------ */
+/*
+ * The counterpart of the device-resident inflaters: a set of HPACK encoding
+ * contexts lives in device memory across calls, and one call turns a batch of
+ * header lists that lie in device memory -- in exactly the layout
+ * nghttp2_amd_hd_dev_inflate_blocks emits -- into wire in device memory.  Per
+ * block the wire, and the table after it, are nghttp2_hd_deflate_hd2's
+ * (nghttp2.h:6127) on a deflater in the same state.  The rules are stated once,
+ * in csrc/hd_deflate_plan.h, for the kernels and for the host twin below.
+ *
+ * A connection's header is the inflaters' nghttp2_amd_hd_dev_conn: max is the
+ * table limit in force (hd_table_bufsize_max), settings_max the connection's
+ * deflate_hd_table_bufsize_max, min_max the smallest limit since the last
+ * block; size, count, head and cur as there; flags holds
+ * NGHTTP2_AMD_HD_DEV_NOTIFY (notify_table_size_change: the next block opens
+ * with the pending size updates).  Beside the ring of 16-byte descriptors a
+ * connection keeps a parallel array of uint32 keys, the FNV-1a hash of each
+ * entry's name: the search's filter (a match is always confirmed on the bytes).
+ */
+#define NGHTTP2_AMD_HD_DEV_NOTIFY 0x8u
+
+/* One field's plan: the representation bytes in front of its string literals
+ * (0x80 | index; 0x40 / 0x00 / 0x10 with a 6- or 4-bit name index or 0), how
+ * many, and which of name and value follow as literals (emit_string's
+ * framing).  block: the block the field was walked in. */
+typedef struct {
+  uint8_t bytes[6];
+  uint8_t nbytes;
+  uint8_t lits; /* NGHTTP2_AMD_HD_PLAN_LIT_* */
+  uint32_t block;
+  uint32_t reserved; /* 0 */
+} nghttp2_amd_hd_plan_rec; /* 16 bytes */
+#define NGHTTP2_AMD_HD_PLAN_LIT_NAME 0x1u
+#define NGHTTP2_AMD_HD_PLAN_LIT_VALUE 0x2u
+/* One block's head: the pending table size updates (at most two integers of 6
+ * bytes with the 5-bit prefix and 0x20). */
+typedef struct {
+  uint8_t bytes[12];
+  uint8_t nbytes;
+  uint8_t reserved[3]; /* 0 */
+} nghttp2_amd_hd_plan_head; /* 16 bytes */
+
+/* out_totals[2] of a device deflate: 0, or why no wire was written */
+#define NGHTTP2_AMD_HD_DEV_OVERFLOW_WIRE 0x1u /* more wire bytes than out_cap */
+#define NGHTTP2_AMD_HD_DEV_OVERFLOW_POOL 0x2u /* more literal bytes than arena_bytes (strings that overlap) */
+/* NGHTTP2_AMD_HD_DEV_OVERFLOW_U32 (0x4): a total does not fit the uint32 offsets */
+
+/*
+ * nconn encoding contexts in device memory, each as nghttp2_hd_deflate_new2
+ * (lib/nghttp2_hd.c:721-748) leaves one for deflate_max[c] (a host array of
+ * nconn values, or NULL for 4096 each): max = min(4096, deflate_max), an empty
+ * table, and NOTIFY set when deflate_max < 4096.  table_bytes follows the
+ * inflaters' rules (a power of two, at least 4096, nconn * 2 * table_bytes at
+ * most UINT32_MAX) and there is no capacity error: every deflate_max[c] must be
+ * at most table_bytes (else NGHTTP2_AMD_ERR_INVALID_ARGUMENT), so the store
+ * holds whatever the limit admits.  _new copies the headers on `stream` and
+ * waits for the copy; _del frees the memory (the caller has synchronised the
+ * streams that use the set).
+ */
+typedef struct nghttp2_amd_hd_dev_deflaters nghttp2_amd_hd_dev_deflaters;
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_deflaters_new(nghttp2_amd_hd_dev_deflaters **set_ptr, uint32_t nconn,
+                                                        uint32_t table_bytes, const uint32_t *deflate_max,
+                                                        void *stream);
+NGHTTP2_AMD_EXTERN void nghttp2_amd_hd_dev_deflaters_del(nghttp2_amd_hd_dev_deflaters *set);
+
+/*
+ * nghttp2_hd_deflate_change_table_size (lib/nghttp2_hd.c:1274-1288) for n
+ * connections: request i sets connection conn[i]'s limit to min(value[i],
+ * deflate_max), lowers min_max to it, sets NOTIFY and evicts; rv[i] = 0, or
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT for a conn[i] >= nconn.  Device arrays, one
+ * lane per request, asynchronous on `stream`; a connection appears at most once
+ * in a call.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_deflaters_change_table_size(nghttp2_amd_hd_dev_deflaters *set,
+                                                                      const uint32_t *conn, const uint32_t *value,
+                                                                      int32_t *rv, uint32_t n, void *stream);
+/* One connection read back, as nghttp2_amd_hd_dev_inflaters_read (synchronises
+ * `stream`; host pointers). */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_deflaters_read(nghttp2_amd_hd_dev_deflaters *set, uint32_t conn,
+                                                         nghttp2_amd_hd_dev_conn *hdr, uint32_t *entries,
+                                                         uint8_t *bytes, void *stream);
+
+/* The device workspace of nghttp2_amd_hd_dev_deflate_blocks: per field slot a
+ * plan record, the name view, token and hash, two literal slots and the wire
+ * lengths; per block a head; per connection 64 bytes and a ring of table_bytes
+ * / 32 descriptors and keys (the call's insertions); the literal pool
+ * (arena_bytes and the pool rule's slack) and the framed literals
+ * (nghttp2_amd_hd_emit_strings_bound(arena_bytes, 2 * nva_cap)) with
+ * emit_strings' own workspace. */
+NGHTTP2_AMD_EXTERN size_t nghttp2_amd_hd_dev_deflate_workspace_size(uint32_t nconn, uint32_t table_bytes,
+                                                                    size_t nva_cap, size_t arena_bytes,
+                                                                    uint32_t nblocks);
+
+/*
+ * A batch of header lists against the set's connections, into wire.
+ *
+ *   nva, nva_cap      : IN: nghttp2_amd_hd_nv records (name_off, name_len,
+ *                       value_off, value_len into arena; flags & 1 is
+ *                       NGHTTP2_NV_FLAG_NO_INDEX; `block` is not read), room
+ *                       for nva_cap of them
+ *   arena, arena_bytes: IN: the strings, and how far arena is readable
+ *   block_nv_off[n+1] : IN: block i's fields are nva[block_nv_off[i],
+ *                       block_nv_off[i+1]); block_nv_off[n], the field count,
+ *                       is read on the device (fields at or past nva_cap are
+ *                       not deflated)
+ *   conn_blk_off[nconn+1], conn_blk[nblocks] : as for the inflaters: a block
+ *                       listed twice is the caller's error (undefined results,
+ *                       no memory outside the arrays touched); a block not
+ *                       listed produces no wire and status 0
+ *   out, out_cap      : OUT: the wire, the blocks back to back in block order
+ *   out_off[n+1]      : OUT: block i's wire is out[out_off[i], out_off[i+1])
+ *   out_status[n]     : OUT: the block's wire bytes
+ *   out_totals[4]     : OUT: {wire bytes, literal pool bytes,
+ *                       NGHTTP2_AMD_HD_DEV_OVERFLOW_* bits, 0}
+ *   workspace         : device scratch, 16-byte aligned, >= the size above
+ *
+ * This is the layout nghttp2_amd_hd_dev_inflate_blocks leaves (name, NUL,
+ * value, NUL per field in field order), so inflate -> (rewrite) -> deflate
+ * never leaves the device.  A string must lie inside arena_bytes and be at
+ * most 0xFFFFFF bytes, else it is deflated as an empty string.  The names'
+ * tokens and hashes come from one nghttp2_amd_hd_name_tokens_len_batch launch
+ * over the names, which examines a name when the names lie at non-decreasing
+ * offsets, a field's name ends before the next field's begins, and arena is
+ * 16-byte aligned and arena_bytes covers the pool rule's slack behind the last
+ * name (align_up(end, 16) + 16); a name it does not examine is hashed and
+ * looked up by the plan kernel itself, with the same result, only slower.
+ *
+ * Overflow is all or nothing, as for the inflaters: when the wire is larger
+ * than out_cap (OVERFLOW_WIRE: out_totals[0] is the need), the literals are
+ * more than arena_bytes (OVERFLOW_POOL, possible only with strings that
+ * overlap: out_totals[1] is the need, out_totals[0] is not), or a total passes
+ * uint32, nothing is written to out and every table is as before the call:
+ * repeat it with room.  out_off and out_status are valid with OVERFLOW_WIRE
+ * alone.  out_cap = 12 * nblocks + 12 * nva_cap + arena_bytes
+ * (nghttp2_hd_deflate_bound summed) cannot overflow.  There is no bad state:
+ * the reference's only deflate failures are allocation and buffer size.
+ *
+ * One clear and ten to twelve launches: the name view, the names' tokens and
+ * hashes, k_deflate_plan (a wave per connection: the fields in order, the
+ * lanes on 64 table entries at a time), the literal slots' scan and gather
+ * (two slots per field slot, an unused one the empty string),
+ * nghttp2_amd_hd_emit_strings_batch on them as it is, the fields' wire
+ * lengths, a one-workgroup scan into out_off, k_place_wire (a wave per 64
+ * fields) and k_commit (a wave per connection that had blocks).  Nothing is
+ * read on the host.
+ *
+ * Device pointers, asynchronous on `stream`; calls on one set are ordered by
+ * the caller.  nblocks == 0 returns 0 and touches nothing.  A NULL set, nva or
+ * arena (with nva_cap > 0), block_nv_off, conn_blk_off, conn_blk, out (with
+ * out_cap > 0), out_off, out_status, out_totals or workspace, an arena or a
+ * workspace that is not 16-byte aligned, a workspace below the size above, an
+ * nva_cap above 0x3FFFFFFF or an arena_bytes above UINT32_MAX is
+ * NGHTTP2_AMD_ERR_INVALID_ARGUMENT.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_dev_deflate_blocks(
+    nghttp2_amd_hd_dev_deflaters *set, const nghttp2_amd_hd_nv *nva, size_t nva_cap, const uint8_t *arena,
+    size_t arena_bytes, const uint32_t *block_nv_off, uint32_t nblocks, const uint32_t *conn_blk_off,
+    const uint32_t *conn_blk, uint8_t *out, size_t out_cap, uint32_t *out_off, int32_t *out_status,
+    uint32_t *out_totals, void *workspace, size_t ws_bytes, void *stream);
+
+/*
+ * The host twin (no GPU call): the same walk over host arrays, for ONE
+ * connection whose blocks are the batch's, in order.  hdr is the connection's
+ * header (_init makes one as _new does), ring its table_bytes / 32 slots of 16
+ * bytes, keys its table_bytes / 32 uint32, store its two buffers (2 *
+ * table_bytes); deflate_max must be at most table_bytes.  recs[block_nv_off[n]]
+ * and heads[n] receive the plan; the table is committed as the device call
+ * commits it.  The wire of block i is heads[i]'s bytes, then per field its
+ * record's bytes, the framed name when LIT_NAME is set and the framed value
+ * when LIT_VALUE is.  _change_table_size is one request of the device call's.
+ */
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_deflate_plan_host_init(nghttp2_amd_hd_dev_conn *hdr, uint32_t table_bytes,
+                                                             uint32_t deflate_max);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_deflate_plan_host_change_table_size(nghttp2_amd_hd_dev_conn *hdr,
+                                                                          const void *ring, uint32_t table_bytes,
+                                                                          uint32_t value);
+NGHTTP2_AMD_EXTERN int nghttp2_amd_hd_deflate_plan_host(nghttp2_amd_hd_dev_conn *hdr, void *ring, uint32_t *keys,
+                                                        uint8_t *store, uint32_t table_bytes,
+                                                        const nghttp2_amd_hd_nv *nva, const uint8_t *arena,
+                                                        size_t arena_bytes, const uint32_t *block_nv_off,
+                                                        uint32_t nblocks, nghttp2_amd_hd_plan_rec *recs,
+                                                        nghttp2_amd_hd_plan_head *heads);
+
+/* ------------------------------------------------------------------ */
 /* Batched HPACK deflate front-end                                      */
 /* ------------------------------------------------------------------ */
 /*

@@ -16,7 +16,9 @@ from .hd import (  # noqa: F401
     CHECK_PATH,
     CHECK_VALUE,
     CHECK_VALUE_RFC9113,
+    DeviceDeflaters,
     DeviceInflaters,
+    HostDeflatePlanner,
     HostReplayInflater,
     HpackDeflater,
     HpackInflater,
@@ -32,6 +34,7 @@ from .hd import (  # noqa: F401
     check_field,
     decode_length,
     lib,
+    pack_header_lists,
     parse_block,
     replay_annotated,
     replay_fields,

@@ -33,6 +33,7 @@
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "../../include/nghttp2_amd_hd_testing.h"
+#include "hd_deflate_plan.h"
 #include "hd_host.h"
 #include "host_threads.h"
 
@@ -41,7 +42,13 @@ namespace {
 using namespace hdhost;  // the static table, hip_ok, DevBuf / PinnedBuf
 const char *const kLayer = "deflate";  // (in hip_ok's messages)
 
-enum Mode { WITH_INDEXING, WITHOUT_INDEXING, NEVER_INDEXING };  // nghttp2_hd.h
+// the indexing modes and decision, the token constants and the prefix integer
+// are hd_deflate_plan.h's, shared with the device deflaters
+using hdplan::Mode;
+using hdplan::NEVER_INDEXING;
+using hdplan::WITH_INDEXING;
+using hdplan::WITHOUT_INDEXING;
+using hdplan::kLastStaticToken;
 
 // the name (which = 0) or value (1) of static entry s is these bytes
 bool static_is(uint32_t s, int which, const uint8_t *p, size_t len) {
@@ -51,28 +58,15 @@ bool static_is(uint32_t s, int which, const uint8_t *p, size_t len) {
 // lookup_token (lib/nghttp2_hd.c:137) and name_hash (:536-547): one FNV-1a
 // pass and a hashed probe (hd_tokens.h), shared with the GPU kernel.
 using hdtok::name_hash;
-// the NGHTTP2_TOKEN_* values (lib/nghttp2_hd.h:57-108) the indexing decision names
-constexpr int32_t kTokenPath = 3, kTokenAge = 20, kTokenAuthorization = 22, kTokenContentLength = 27,
-                  kTokenCookie = 31, kTokenEtag = 33, kTokenIfModifiedSince = 39, kTokenIfNoneMatch = 40,
-                  kTokenLocation = 45, kTokenSetCookie = 54;
-constexpr int32_t kLastStaticToken = 60;  // NGHTTP2_TOKEN_WWW_AUTHENTICATE
-
 struct Entry {
   std::string name, value;
   uint32_t hash;
 };
 
-// RFC 7541 5.1 prefix integer (encode_length, lib/nghttp2_hd.c:840-863)
+// RFC 7541 5.1 prefix integer (hdplan::put_int), appended to out
 void put_int(std::string &out, uint32_t n, uint32_t prefix, uint8_t first) {
-  const uint32_t k = (1u << prefix) - 1u;
-  if (n < k) {
-    out.push_back((char)(first | n));
-    return;
-  }
-  out.push_back((char)(first | k));
-  n -= k;
-  for (; n >= 128u; n >>= 7) out.push_back((char)(0x80u | (n & 0x7Fu)));
-  out.push_back((char)n);
+  const hdplan::Packed p = hdplan::put_int(n, prefix, first);
+  for (uint32_t i = 0; i < p.n; ++i) out.push_back((char)(uint8_t)(p.v >> (8u * i)));
 }
 
 }  // namespace
@@ -209,17 +203,9 @@ int stage_name_tokens(const nghttp2_amd_nv *names, uint32_t nf, void *stream, st
   return 0;
 }
 
-// deflate_nv's indexing mode (lib/nghttp2_hd.c:1373-1400): never index
-// authorization, short cookies and fields flagged NO_INDEX; else
-// hd_deflate_decide_indexing (:1358-1371).
+// deflate_nv's indexing mode (hdplan::decide_indexing)
 Mode decide_indexing(int32_t token, const nghttp2_amd_nv &nv, size_t bufsize_max) {
-  if (token == kTokenAuthorization || (token == kTokenCookie && nv.valuelen < 20) || (nv.flags & 1u))
-    return NEVER_INDEXING;
-  if (token == kTokenPath || token == kTokenAge || token == kTokenContentLength || token == kTokenEtag ||
-      token == kTokenIfModifiedSince || token == kTokenIfNoneMatch || token == kTokenLocation ||
-      token == kTokenSetCookie || nv.namelen + nv.valuelen + kEntryOverhead > bufsize_max * 3 / 4)
-    return WITHOUT_INDEXING;
-  return WITH_INDEXING;
+  return hdplan::decide_indexing(token, nv.namelen, nv.valuelen, nv.flags, bufsize_max);
 }
 
 // search_hd_table (lib/nghttp2_hd.c:1225-1249): the dynamic table newest

@@ -1457,3 +1457,270 @@ def deflate_blocks(deflaters, header_lists, stream=None, out_cap=None):
     oo = out_off.tolist()
     raw = out[:oo[nb]].tobytes()
     return st[:nb].tolist(), [raw[oo[i]:oo[i + 1]] for i in range(nb)]
+
+
+# ---------------------------------------------------------------------------
+# Device-resident deflaters (nghttp2_amd_hd_dev_deflate*, nghttp2_amd_hd_deflate_plan_host)
+# ---------------------------------------------------------------------------
+DEV_NOTIFY = 0x8
+DEV_OVERFLOW_WIRE, DEV_OVERFLOW_POOL = 0x1, 0x2  # (DEV_OVERFLOW_U32 is the inflaters')
+PLAN_LIT_NAME, PLAN_LIT_VALUE = 0x1, 0x2
+PLAN_REC_DTYPE = np.dtype([("bytes", "u1", (6,)), ("nbytes", "u1"), ("lits", "u1"), ("block", "<u4"),
+                           ("reserved", "<u4")])
+PLAN_HEAD_DTYPE = np.dtype([("bytes", "u1", (12,)), ("nbytes", "u1"), ("reserved", "u1", (3,))])
+assert PLAN_REC_DTYPE.itemsize == 16 and PLAN_HEAD_DTYPE.itemsize == 16
+
+
+def _dev_deflate_lib():
+    L = _replay_lib()
+    if not getattr(L, "_dev_deflate_bound", False):
+        vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
+        L.nghttp2_amd_hd_dev_deflaters_new.argtypes = [ctypes.POINTER(vp), u32, u32, vp, vp]
+        L.nghttp2_amd_hd_dev_deflaters_del.argtypes = [vp]
+        L.nghttp2_amd_hd_dev_deflaters_del.restype = None
+        L.nghttp2_amd_hd_dev_deflaters_change_table_size.argtypes = [vp, vp, vp, vp, u32, vp]
+        L.nghttp2_amd_hd_dev_deflaters_read.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.nghttp2_amd_hd_dev_deflate_workspace_size.argtypes = [u32, u32, sz, sz, u32]
+        L.nghttp2_amd_hd_dev_deflate_workspace_size.restype = sz
+        L.nghttp2_amd_hd_dev_deflate_blocks.argtypes = [vp, vp, sz, vp, sz, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp,
+                                                        sz, vp]
+        L.nghttp2_amd_hd_deflate_plan_host_init.argtypes = [vp, u32, u32]
+        L.nghttp2_amd_hd_deflate_plan_host_change_table_size.argtypes = [vp, vp, u32, u32]
+        L.nghttp2_amd_hd_deflate_plan_host.argtypes = [vp, vp, vp, vp, u32, vp, vp, sz, vp, u32, vp, vp]
+        L._dev_deflate_bound = True
+    return L
+
+
+def pack_header_lists(header_lists):
+    """Host header lists (each [(name, value[, flags])]) in the layout
+    nghttp2_amd_hd_dev_inflate_blocks emits and the device deflaters take:
+    (nva, arena, block_nv_off) numpy arrays -- _NV_DTYPE records, the arena of
+    name, NUL, value, NUL per field with the pool rule's slack behind it
+    (zeros), and uint32 offsets."""
+    flat = [(bytes(h[0]), bytes(h[1]), h[2] if len(h) > 2 else 0, b)
+            for b, hl in enumerate(header_lists) for h in hl]
+    nva = np.zeros(max(1, len(flat)), _NV_DTYPE)
+    parts, at = [], 0
+    for k, (n, v, fl, b) in enumerate(flat):
+        nva[k] = (b, at, len(n), at + len(n) + 1, len(v), fl)
+        parts += [n, b"\0", v, b"\0"]
+        at += len(n) + len(v) + 2
+    arena = np.zeros((at + 15) // 16 * 16 + 32, np.uint8)
+    arena[:at] = np.frombuffer(b"".join(parts), np.uint8)
+    off = np.zeros(len(header_lists) + 1, np.uint32)
+    np.cumsum([len(hl) for hl in header_lists], out=off[1:])
+    return nva[:len(flat)], arena, off
+
+
+class HostDeflatePlanner:
+    """One connection of a DeviceDeflaters set on the host
+    (nghttp2_amd_hd_deflate_plan_host; no GPU): the same header, ring, keys
+    and stores, walked by the same code.  What the device results are
+    compared with."""
+
+    def __init__(self, table_bytes=4096, deflate_max=4096):
+        self.L = _dev_deflate_lib()
+        self.table_bytes = int(table_bytes)
+        self.hdr = np.zeros(1, DEV_CONN_DTYPE)
+        self.ring = np.zeros(self.table_bytes // 32 * 4, np.uint32)
+        self.keys = np.zeros(self.table_bytes // 32, np.uint32)
+        self.store = np.zeros(2 * self.table_bytes, np.uint8)
+        _check(self.L.nghttp2_amd_hd_deflate_plan_host_init(self.hdr.ctypes.data, self.table_bytes, int(deflate_max)),
+               "deflate_plan_host_init")
+
+    def change_table_size(self, value):
+        _check(self.L.nghttp2_amd_hd_deflate_plan_host_change_table_size(
+            self.hdr.ctypes.data, self.ring.ctypes.data, self.table_bytes, int(value)),
+            "deflate_plan_host_change_table_size")
+        return 0
+
+    def plan_packed(self, nva, arena, block_nv_off):
+        """The plan of packed lists (pack_header_lists' arrays), every block
+        on this connection in order: (recs, heads) as PLAN_REC_DTYPE /
+        PLAN_HEAD_DTYPE arrays."""
+        n = len(block_nv_off) - 1
+        nva = np.ascontiguousarray(nva, _NV_DTYPE)
+        block_nv_off = np.ascontiguousarray(block_nv_off, np.uint32)
+        recs = np.zeros(max(1, len(nva)), PLAN_REC_DTYPE)
+        heads = np.zeros(max(1, n), PLAN_HEAD_DTYPE)
+        _check(self.L.nghttp2_amd_hd_deflate_plan_host(
+            self.hdr.ctypes.data, self.ring.ctypes.data, self.keys.ctypes.data, self.store.ctypes.data,
+            self.table_bytes, nva.ctypes.data if len(nva) else None, arena.ctypes.data, len(arena),
+            block_nv_off.ctypes.data, n, recs.ctypes.data, heads.ctypes.data), "deflate_plan_host")
+        return recs[:len(nva)], heads[:n]
+
+    def plan(self, header_lists):
+        """plan_packed of host header lists; also returns the packed arrays:
+        (recs, heads, nva, arena, block_nv_off)."""
+        nva, arena, off = pack_header_lists(header_lists)
+        return self.plan_packed(nva, arena, off) + (nva, arena, off)
+
+    def table(self):
+        """[(name, value)] of the dynamic table, most recent first."""
+        h = self.hdr[0]
+        slots = self.table_bytes // 32
+        ring = self.ring.reshape(-1, 4)
+        raw = self.store[int(h["cur"]) * self.table_bytes:][:self.table_bytes].tobytes()
+        out = []
+        for i in range(int(h["count"])):
+            a, b, c, d = (int(x) for x in ring[(int(h["head"]) + i) % slots])
+            out.append((raw[a:a + (b & 0xFFFFFF)], raw[c:c + (d & 0xFFFFFF)]))
+        return out
+
+    def table_size(self):
+        return int(self.hdr[0]["size"])
+
+    def table_max(self):
+        return int(self.hdr[0]["max"])
+
+    def state(self):
+        return self.table(), self.table_size(), self.table_max()
+
+
+class DeviceDeflaters:
+    """nconn HPACK encoding contexts in device memory
+    (nghttp2_amd_hd_dev_deflaters): header lists that lie on the device --
+    a ReplayedBlocks of DeviceInflaters, or packed (nva, arena, block_nv_off)
+    tensors -- into wire on the device.  deflate_max is one value for every
+    connection, a sequence of nconn, or None for 4096; each at most
+    table_bytes.  Calls on one set are ordered by their stream."""
+
+    def __init__(self, nconn, table_bytes=4096, deflate_max=None, device=None, stream=None):
+        import torch
+        self.torch = torch
+        self.device = torch.device(device if device is not None else "cuda")
+        self.L = _dev_deflate_lib()
+        self.nconn, self.table_bytes = int(nconn), int(table_bytes)
+        self._ws = None
+        dm = None
+        if deflate_max is not None:
+            dm = np.full(self.nconn, deflate_max, np.uint32) if np.isscalar(deflate_max) else \
+                np.ascontiguousarray(deflate_max, np.uint32)
+            if len(dm) != self.nconn:
+                raise ValueError("deflate_max: one value per connection")
+        p = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.L.nghttp2_amd_hd_dev_deflaters_new(ctypes.byref(p), self.nconn, self.table_bytes,
+                                                           dm.ctypes.data if dm is not None else None,
+                                                           _stream(stream)), "dev_deflaters_new")
+        self.p = p
+
+    def __del__(self):
+        if getattr(self, "p", None):
+            self.torch.cuda.synchronize(self.device)
+            self.L.nghttp2_amd_hd_dev_deflaters_del(self.p)
+            self.p = None
+
+    _dev = DeviceInflaters._dev
+    csr = DeviceInflaters.csr
+
+    def change_table_size(self, conns, values, stream=None):
+        """nghttp2_hd_deflate_change_table_size for connection conns[i] with
+        values[i]; a connection appears at most once.  Returns the rv's as a
+        device int32 tensor (all 0)."""
+        conns = [int(c) for c in conns]
+        if len(set(conns)) != len(conns):
+            raise ValueError("change_table_size: a connection appears more than once")
+        if any(c < 0 or c >= self.nconn for c in conns):
+            raise ValueError("change_table_size: connection out of range")
+        n = len(conns)
+        rv = self.torch.zeros(max(1, n), dtype=self.torch.int32, device=self.device)
+        if n:
+            c = self._dev(conns, np.uint32)
+            v = self._dev([int(x) for x in values], np.uint32)
+            _check(self.L.nghttp2_amd_hd_dev_deflaters_change_table_size(self.p, _p(c), _p(v), _p(rv), n,
+                                                                         _stream(stream)),
+                   "dev_deflaters_change_table_size")
+        return rv[:n]
+
+    def _read(self, c, stream=None):
+        hdr = np.zeros(1, DEV_CONN_DTYPE)
+        ent = np.zeros(self.table_bytes // 32 * 4, np.uint32)
+        raw = np.zeros(self.table_bytes, np.uint8)
+        _check(self.L.nghttp2_amd_hd_dev_deflaters_read(self.p, int(c), hdr.ctypes.data, ent.ctypes.data,
+                                                        raw.ctypes.data, _stream(stream)), "dev_deflaters_read")
+        return hdr[0], ent, raw.tobytes()
+
+    def table(self, c, stream=None):
+        """[(name, value)] of connection c's dynamic table, most recent first
+        (synchronises the stream)."""
+        return _conn_state(*self._read(c, stream))
+
+    def table_size(self, c, stream=None):
+        return int(self._read(c, stream)[0]["size"])
+
+    def table_max(self, c, stream=None):
+        return int(self._read(c, stream)[0]["max"])
+
+    def state(self, c, stream=None):
+        """(table, size, max) in one read."""
+        h, ent, raw = self._read(c, stream)
+        return _conn_state(h, ent, raw), int(h["size"]), int(h["max"])
+
+    def upload(self, header_lists):
+        """pack_header_lists' arrays as device tensors (nva, arena,
+        block_nv_off), for deflate."""
+        nva, arena, off = pack_header_lists(header_lists)
+        t = self.torch
+        nv = np.ascontiguousarray(nva).view(np.uint8) if len(nva) else np.zeros(_NV_DTYPE.itemsize, np.uint8)
+        return (t.from_numpy(nv.copy()).to(self.device), t.from_numpy(arena).to(self.device),
+                t.from_numpy(off.view(np.int32)).to(self.device))
+
+    @staticmethod
+    def bound(nblocks, nva_cap, arena_bytes):
+        """An out_cap that cannot overflow: nghttp2_hd_deflate_bound summed."""
+        return 12 * nblocks + 12 * nva_cap + arena_bytes
+
+    def deflate(self, fields, conn_blk_off, conn_blk, out_cap=None, stream=None, out=None):
+        """nghttp2_amd_hd_dev_deflate_blocks: fields is a ReplayedBlocks or
+        (nva, arena, block_nv_off) device tensors, conn_blk_off / conn_blk
+        the CSR of csr().  Returns (out, out_off, out_status, totals) device
+        tensors: block i's wire is out[out_off[i]:out_off[i+1]], totals =
+        {wire bytes, literal pool bytes, DEV_OVERFLOW_* bits, 0}.  Nothing is
+        read back; without an out_cap the bound that cannot overflow is used,
+        with one an overflow is the caller's to see in totals[2] (no wire, no
+        table changed: repeat with room).  out: a uint8 device tensor to
+        write the wire to (its size is the out_cap when none is given)."""
+        torch = self.torch
+        if isinstance(fields, ReplayedBlocks):
+            nva, arena, nv_off = fields.nva, fields.arena, fields.block_nv_off
+        else:
+            nva, arena, nv_off = fields
+        n = nv_off.numel() - 1
+        nva_cap = nva.numel() * nva.element_size() // _NV_DTYPE.itemsize
+        # how far the arena is readable: to the end of its allocation
+        arena_bytes = arena.untyped_storage().nbytes() - arena.storage_offset() * arena.element_size()
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if out is not None and out_cap is None:
+            out_cap = out.numel()
+        cap = self.bound(n, nva_cap, arena_bytes) if out_cap is None else int(out_cap)
+        if out is not None and (out.numel() < cap or out.dtype != torch.uint8):
+            raise ValueError("out: a uint8 tensor of at least out_cap bytes")
+        need = self.L.nghttp2_amd_hd_dev_deflate_workspace_size(self.nconn, self.table_bytes, nva_cap, arena_bytes, n)
+        with torch.cuda.stream(s):
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if out is None:
+                out = torch.empty(max(1, cap), dtype=torch.uint8, device=self.device)
+            out_off = torch.zeros(n + 1, dtype=torch.int32, device=self.device)
+            out_status = torch.zeros(max(1, n), dtype=torch.int32, device=self.device)
+            totals = torch.zeros(4, dtype=torch.int32, device=self.device)
+        rv = self.L.nghttp2_amd_hd_dev_deflate_blocks(
+            self.p, _p(nva), nva_cap, _p(arena), arena_bytes, _p(nv_off), n, _p(conn_blk_off), _p(conn_blk),
+            _p(out), cap, _p(out_off), _p(out_status), _p(totals), _p(self._ws), self._ws.numel(),
+            ctypes.c_void_p(s.cuda_stream))
+        _check(rv, "dev_deflate_blocks")
+        return out[:cap], out_off, out_status[:n], totals
+
+
+def deflated_wire(out, out_off, totals=None):
+    """A device deflate's wire read back (synchronises): [bytes] per block.
+    With the call's totals, a call that overflowed (totals[2] != 0: out was
+    not written) raises instead of returning what out happened to hold."""
+    if totals is not None:
+        t = totals.cpu().numpy().view(np.uint32).tolist()
+        if t[2]:
+            raise RuntimeError("nghttp2_amd: the deflate overflowed (totals = %r): no wire was written" % (t,))
+    off = out_off.cpu().numpy().view(np.uint32).tolist()
+    raw = out[:off[-1]].cpu().numpy().tobytes()
+    return [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]

@@ -50,6 +50,13 @@
            the row sets: run it alone, or first).  Several runs; the spread
            of the runs' medians is reported.
 
+  dev_deflate  nghttp2_amd_hd_dev_deflate_blocks on the 2,048-list batch with
+           resident fields against nghttp2_amd_hd_deflate_blocks on the same
+           lists from host memory, alternated, fresh contexts each run; two
+           batches: lists that repeat (indexed: the search) and all new
+           values (insertions and evictions).  dev_deflate_repeat and
+           dev_deflate_new run one batch (for a kernel trace of it).
+
 With NGHTTP2_AMD_OTHER_LIB the names, check, names_len and http_facts rows
 also make the same call from that build, alternated call by call with this
 build's on the same resident pools (the `other_*` figures).
@@ -1230,6 +1237,154 @@ def bench_dev_inflate_http(nconn=256, per_conn=8, fields=16, runs=5, steps=20):
                     "nghttp2_amd_hd_inflate_blocks_http on the same blocks from host memory, wall time"}
 
 
+def make_lists(nconn, per_conn, fields_per_block, repeat, seed=7):
+    """make_blocks' batch as header lists: two static fields and
+    `fields_per_block` literal fields per list, block r of every connection
+    before block r + 1 of any.  `repeat`: a connection sends one list per_conn
+    times (names of its own, values of at most 64 bytes, so the table holds
+    the list and from the second block on every field is indexed: the search
+    is the work).  Else every value is new (six names): every field is a
+    name match, an insertion and evictions."""
+    from nghttp2_amd import workloads as W
+    rng = np.random.Generator(np.random.PCG64(seed))
+    nv = nconn * fields_per_block * (1 if repeat else per_conn)
+    pool, off = W.gen_mixed_values(nv, seed=seed, hi=64 if repeat else 120)
+    names = [b"cookie", b"user-agent", b"x-request-id", b"accept", b"referer", b"x-trace"]
+    lists, conns = [], []
+    v = 0
+    for r in range(per_conn):
+        for c in range(nconn):
+            hl = [(b":method", b"GET"), (b":scheme", b"https")]
+            for k in range(fields_per_block):
+                if repeat:
+                    i = c * fields_per_block + k
+                    hl.append((b"x-h%02d" % k, bytes(pool[off[i]:off[i + 1]])))
+                else:
+                    hl.append((names[rng.integers(0, len(names))], bytes(pool[off[v]:off[v + 1]])))
+                    v += 1
+            lists.append(hl)
+            conns.append(c)
+    return lists, conns
+
+
+def bench_dev_deflate(nconn=256, per_conn=8, fields=16, runs=5, steps=20, batches=("repeat", "new")):
+    """nghttp2_amd_hd_dev_deflate_blocks on bench_dev_inflate's batch shape
+    (2,048 lists, 256 connections, 18 fields; resident fields, the C call on
+    tensors allocated once) against nghttp2_amd_hd_deflate_blocks on the same
+    lists from host memory, in one process, alternating call by call with
+    fresh contexts each run: each run times `steps` device calls between HIP
+    events and as wall time around the call and one stream synchronisation,
+    and `steps` host calls as wall time.  Two batches (make_lists): `repeat`,
+    the steady state, and `new`.  The row reports each run's medians and the
+    spread of those medians over the runs."""
+    import ctypes
+    import statistics
+    import torch
+    import nghttp2_amd
+    from nghttp2_amd import hd
+    dev = torch.device("cuda:0")
+    L = hd._dev_deflate_lib()
+    LD = hd._deflate_lib()
+    p = hd._p
+    i32, u8 = torch.int32, torch.uint8
+    out_rows = {}
+    for batch in batches:
+        lists, conns = make_lists(nconn, per_conn, fields, batch == "repeat")
+        m = len(lists)
+        first = nghttp2_amd.DeviceDeflaters(nconn, 4096)
+        tn, ta, to = first.upload(lists)
+        nf = sum(len(hl) for hl in lists)
+        ab = ta.numel()
+        csr_off, csr_blk = first.csr(conns)
+        # the results to hold the timed calls to: the host deflater's on fresh contexts
+        ds = [nghttp2_amd.HpackDeflater() for _ in range(nconn)]
+        hst, hwire = nghttp2_amd.deflate_blocks([ds[c] for c in conns], lists)
+        r0 = first.deflate((tn, ta, to), csr_off, csr_blk)
+        assert hd.deflated_wire(r0[0], r0[1]) == hwire
+        cap = first.bound(m, nf, ab)
+        out = torch.empty(cap, dtype=u8, device=dev)
+        out_off, out_status = torch.empty(m + 1, dtype=i32, device=dev), torch.empty(m, dtype=i32, device=dev)
+        out_totals = torch.empty(4, dtype=i32, device=dev)
+        ws = torch.empty(L.nghttp2_amd_hd_dev_deflate_workspace_size(nconn, 4096, nf, ab, m), dtype=u8, device=dev)
+        st = hd._stream(None)
+        cur = {}
+
+        def device():
+            rv = L.nghttp2_amd_hd_dev_deflate_blocks(cur["set"].p, p(tn), nf, p(ta), ab, p(to), m, p(csr_off),
+                                                     p(csr_blk), p(out), cap, p(out_off), p(out_status),
+                                                     p(out_totals), p(ws), ws.numel(), st)
+            assert rv == 0
+
+        # the host call's arguments, built once: an nghttp2_nv array over one joined buffer
+        flat = [f for hl in lists for f in hl]
+        joined = np.frombuffer(b"".join(x for n_, v_ in flat for x in (n_, v_)), np.uint8)
+        plen = np.fromiter((len(x) for n_, v_ in flat for x in (n_, v_)), np.uint64, count=2 * nf)
+        pstart = np.zeros(2 * nf, np.uint64)
+        np.cumsum(plen[:-1], out=pstart[1:])
+        hnva = np.zeros(nf, hd._NVIN_DTYPE)
+        hnva["name"], hnva["value"] = pstart[0::2] + np.uint64(joined.ctypes.data), pstart[1::2] + np.uint64(joined.ctypes.data)
+        hnva["namelen"], hnva["valuelen"] = plen[0::2], plen[1::2]
+        hoffs = np.zeros(m + 1, np.uint32)
+        np.cumsum([len(hl) for hl in lists], out=hoffs[1:])
+        hout, hout_off, hstat = np.empty(cap, np.uint8), np.zeros(m + 1, np.uint32), np.zeros(m, np.int32)
+        vp = ctypes.c_void_p
+
+        def host():
+            t0 = time.perf_counter()
+            rv = LD.nghttp2_amd_hd_deflate_blocks(vp(cur["dp"].ctypes.data), m, vp(hnva.ctypes.data),
+                                                  vp(hoffs.ctypes.data), vp(hout.ctypes.data), cap,
+                                                  vp(hout_off.ctypes.data), vp(hstat.ctypes.data), st)
+            assert rv == 0
+            return (time.perf_counter() - t0) * 1e6
+
+        s = torch.cuda.current_stream()
+        per_run = []
+        for _ in range(runs):
+            cur["set"] = nghttp2_amd.DeviceDeflaters(nconn, 4096)
+            cur["ds"] = [nghttp2_amd.HpackDeflater() for _ in range(nconn)]
+            cur["dp"] = np.fromiter((cur["ds"][c].p.value for c in conns), np.uint64, count=m)
+            for _ in range(3):
+                device()
+                host()
+            ev, hostt, wall = [], [], []
+            for _ in range(steps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(s)
+                device()
+                b.record(s)
+                ev.append((a, b))
+                hostt.append(host())
+            torch.cuda.synchronize()
+            for _ in range(steps):
+                s.synchronize()
+                t0 = time.perf_counter()
+                device()
+                s.synchronize()
+                wall.append((time.perf_counter() - t0) * 1e6)
+                host()
+            t = [a.elapsed_time(b) * 1e3 for a, b in ev]
+            per_run.append({"device_us_best": round(min(t), 2), "device_us_median": round(float(np.median(t)), 2),
+                            "device_wall_us_median": round(statistics.median(wall), 1),
+                            "deflate_call_us_median": round(statistics.median(hostt), 1)})
+        # the timed calls' last results: both sides made the same calls on contexts of the same age
+        tot = out_totals.cpu().numpy().view(np.uint32).tolist()
+        oo = hout_off.tolist()
+        assert tot[2] == 0 and tot[0] == oo[m]
+        assert hd.deflated_wire(out, out_off) == [hout[oo[i]:oo[i + 1]].tobytes() for i in range(m)]
+        spread = {}
+        for k in [k for k in per_run[0] if k.endswith("_median")]:
+            v = [r[k] for r in per_run]
+            spread[k] = {"median": round(statistics.median(v), 1), "min": min(v), "max": max(v)}
+        out_rows[batch] = {"lists": m, "connections": nconn, "fields": nf, "arena_bytes": ab, "wire_bytes": tot[0],
+                           "literal_pool_bytes": tot[1], "runs": runs, "steps": steps, "over_runs": spread,
+                           "per_run": per_run}
+    out_rows["note"] = ("device: nghttp2_amd_hd_dev_deflate_blocks, the C call on preallocated tensors with resident "
+                        "fields; HIP events around the call (_us_*) and wall time around the call and one stream "
+                        "synchronisation (_wall_us_median); deflate_call: nghttp2_amd_hd_deflate_blocks on the same "
+                        "lists from host memory, wall time; the last timed calls' wires are asserted equal")
+    return out_rows
+
+
 def _fresh_for(conns, nconn):
     import nghttp2_amd
     infs = [nghttp2_amd.HpackInflater() for _ in range(nconn)]
@@ -1252,5 +1407,8 @@ if __name__ == "__main__":
            "parse": bench_parse,
            "dev_inflate": bench_dev_inflate,
            "dev_inflate_http": bench_dev_inflate_http,
+           "dev_deflate": bench_dev_deflate,
+           "dev_deflate_repeat": lambda: bench_dev_deflate(batches=("repeat",)),
+           "dev_deflate_new": lambda: bench_dev_deflate(batches=("new",)),
            "names_short": lambda: bench_names(long_frac=0.0)}
     print(json.dumps({r: fns[r]() for r in rows}, indent=1))
