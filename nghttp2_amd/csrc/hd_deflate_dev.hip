@@ -5,7 +5,9 @@
 // contexts lives in device memory: per connection a 32-byte header, a ring of
 // table_bytes / 32 entry descriptors with a parallel array of keys (the FNV-1a
 // hash of each entry's name) and two byte stores of table_bytes -- the
-// inflaters' layout plus the keys.
+// inflaters' layout plus the keys.  The set, the wave's copy of byte runs and
+// the commit are hd_devtable.h's, shared with the device inflaters; the host's
+// commit and the ring's read-out are hd_replay.h's.
 //
 // nghttp2_amd_hd_dev_deflate_blocks, one clear of the plan and the launches:
 //   k_name_view     a lane per field slot: the names as a string view of the
@@ -37,8 +39,8 @@
 //                   (head and fields), out_off, out_status, out_totals.
 //   k_place_wire    a lane per block copies its head, a wave per 64 fields the
 //                   representation bytes and the framed literals, in wire order.
-//   k_commit        a wave per connection that had blocks: hd_replay.hip's
-//                   commit plus the keys of the entries that entered.
+//   k_commit        a wave per connection that had blocks: hdtable::commit
+//                   over the two stores, with the keys of the entries that entered.
 // With an overflow bit in out_totals[2], k_place_wire and k_commit do nothing:
 // no wire is written and every table is as before the call.
 // Every store to global memory is plain C++ (vector stores).
@@ -46,21 +48,15 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "hd_deflate_plan.h"
+#include "hd_devtable.h"
 #include "hd_host.h"
 #include "hd_scan.h"
 
-struct nghttp2_amd_hd_dev_deflaters {
-  uint32_t nconn, table_bytes;
-  hdreplay::Conn *hdr;    // [nconn]
-  hdreplay::Entry *ring;  // [nconn][table_bytes / 32]
-  uint32_t *key;          // [nconn][table_bytes / 32]
-  uint8_t *store;         // [nconn][2][table_bytes]
-};
+struct nghttp2_amd_hd_dev_deflaters : hdtable::Set {};
 
 static_assert(sizeof(nghttp2_amd_hd_plan_rec) == 16 && sizeof(nghttp2_amd_hd_plan_head) == 16,
               "the plan's layouts are part of the ABI");
@@ -76,23 +72,17 @@ using hdreplay::Entry;
 using hdreplay::Ref;
 using hdreplay::Table;
 using hdscan::SC_WG;
+using hdtable::Left;
+using hdtable::Span;
 
 constexpr uint32_t PL_WG = 64;   // k_deflate_plan, k_commit: one wave, one connection
 constexpr uint32_t LN_WG = 256;  // the kernels with a lane per field slot
-constexpr uint32_t CS_WG = 64;   // k_change_size
 constexpr uint32_t kMaxCap = 0x3FFFFFFFu;  // 2 * nva_cap + 1 literal offsets are uint32 counts
 constexpr uint32_t kBitWire = NGHTTP2_AMD_HD_DEV_OVERFLOW_WIRE, kBitPool = NGHTTP2_AMD_HD_DEV_OVERFLOW_POOL,
                    kBitU32 = NGHTTP2_AMD_HD_DEV_OVERFLOW_U32;
 
 __constant__ hdhost::StaticPool d_static = hdhost::kStaticPool;
 __constant__ hdtok::Table d_tokens = hdtok::kTable;
-
-// What k_deflate_plan leaves k_commit for a connection that had blocks.
-struct Left {  // 64 bytes
-  Conn h;
-  uint32_t nnew, nhead, nold, walked;
-  uint32_t pad[4];
-};
 
 // The workspace.  recs, heads and lit_len are one span, cleared by the call: a
 // field or block no connection lists has no bytes and no literal.
@@ -179,35 +169,28 @@ __global__ __launch_bounds__(LN_WG) void k_name_view(const nghttp2_amd_hd_nv *__
   if (k < cap) name_len[k] = nl;
 }
 
-__global__ __launch_bounds__(CS_WG) void k_change_size(Conn *__restrict__ hdr, const Entry *__restrict__ ring,
-                                                       uint32_t nconn, uint32_t table_bytes,
-                                                       const uint32_t *__restrict__ conn,
-                                                       const uint32_t *__restrict__ value, int32_t *__restrict__ rv,
-                                                       uint32_t n) {
-  const uint32_t i = blockIdx.x * CS_WG + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t c = conn[i];
-  if (c >= nconn) {
-    rv[i] = NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-    return;
+struct ChangeSize {  // hdtable::k_change_size's rule
+  __device__ int operator()(Conn *h, const Entry *ring, uint32_t table_bytes, uint32_t v) const {
+    hdplan::change_table_size(h, ring, table_bytes, v);
+    return 0;
   }
-  Conn h = hdr[c];
-  hdplan::change_table_size(&h, ring + (size_t)c * (table_bytes / hdreplay::kOverhead), table_bytes, value[i]);
-  hdr[c] = h;
-  rv[i] = 0;
-}
+};
 
 // The two stores a deflater's Ref can name, with their sizes: a Ref that
-// reaches past its store is not read.
+// reaches past its store is not read (hdtable::wave_copy's and
+// hdtable::commit's policy).
 struct Stores {
   Bytes by;
   uint64_t store_bytes, arena_bytes;
+  __device__ bool ok(Ref r) const {
+    const uint32_t src = hdreplay::ref_src(r);
+    const uint64_t lim = src == hdplan::SRC_ARENA ? arena_bytes : src == hdreplay::SRC_TABLE ? store_bytes : 0u;
+    return (uint64_t)r.off + hdreplay::ref_len(r) <= lim;
+  }
+  __device__ const uint8_t *ptr(uint32_t off, uint32_t ls) const { return hdplan::ref_ptr(by, Ref{off, ls}); }
+  __device__ uint32_t len(uint32_t ls) const { return ls & 0xFFFFFFu; }
+  __device__ bool readable(uint32_t, uint32_t) const { return true; }  // (a Ref that is ok)
 };
-__device__ __forceinline__ bool ref_ok(const Stores &s, Ref r) {
-  const uint32_t src = hdreplay::ref_src(r);
-  const uint64_t lim = src == hdplan::SRC_ARENA ? s.arena_bytes : src == hdreplay::SRC_TABLE ? s.store_bytes : 0u;
-  return (uint64_t)r.off + hdreplay::ref_len(r) <= lim;
-}
 
 // The dynamic table searched by a wave (hdplan::search_serial's result): 64
 // entries per trip, newest first.  A lane takes one entry: key, descriptor,
@@ -234,7 +217,7 @@ struct WaveSearch {
       if (i < count) {
         const uint32_t key = hdplan::key_get(t, k, i);
         e = hdreplay::table_get(t, i);
-        cand = key == f.hash && hdreplay::ref_len(e.name) == f.name_len && ref_ok(s, e.name) && ref_ok(s, e.value);
+        cand = key == f.hash && hdreplay::ref_len(e.name) == f.name_len && s.ok(e.name) && s.ok(e.value);
       }
       uint64_t cm = __ballot(cand);
       while (cm) {
@@ -351,25 +334,6 @@ __global__ __launch_bounds__(SC_WG) void k_lit_scan(const uint32_t *lit_len, uin
   }
 }
 
-// The wave copies the byte runs of the lanes with `has`, one after the other,
-// its lanes on consecutive bytes: lane l's is from[off, off + len) to
-// to[d, ...).  Every load is below from_cap, every store below to_cap.
-__device__ __forceinline__ void wave_copy(bool has, const uint8_t *from, uint64_t from_cap, uint32_t off, uint32_t len,
-                                          uint8_t *to, uint64_t to_cap, uint64_t d, uint32_t lane) {
-  uint64_t m = __ballot(has && len);
-  while (m) {
-    const int l = __builtin_ctzll(m);
-    m &= m - 1ull;
-    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)off, l);
-    const uint32_t nb = (uint32_t)__builtin_amdgcn_readlane((int)len, l);
-    const uint32_t dlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)d, l);
-    const uint32_t dhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(d >> 32), l);
-    const uint64_t at = ((uint64_t)dhi << 32) | dlo;
-    for (uint32_t b = lane; b < nb; b += 64u)
-      if ((uint64_t)o + b < from_cap && at + b < to_cap) to[at + b] = from[(uint64_t)o + b];
-  }
-}
-
 __global__ __launch_bounds__(LN_WG) void k_lit_gather(const nghttp2_amd_hd_nv *__restrict__ nva, uint32_t cap,
                                                       const uint8_t *__restrict__ arena, uint32_t arena_bytes,
                                                       const uint32_t *__restrict__ lit_off,
@@ -382,7 +346,7 @@ __global__ __launch_bounds__(LN_WG) void k_lit_gather(const nghttp2_amd_hd_nv *_
     len = lit_off[j + 1u] - at;
     if (len) off = j & 1u ? nva[j >> 1].value_off : nva[j >> 1].name_off;
   }
-  wave_copy(len != 0u, arena, arena_bytes, off, len, pool, pool_cap, at, lane);
+  hdtable::wave_copy(Span{arena, arena_bytes}, len != 0u, Ref{off, len}, (uint64_t)at, pool, pool_cap, lane);
 }
 
 __global__ __launch_bounds__(LN_WG) void k_field_len(const uint4 *__restrict__ recs, uint32_t cap,
@@ -477,9 +441,10 @@ __global__ __launch_bounds__(LN_WG) void k_place_wire(const uint32_t *__restrict
     }
   }
   const bool ln = has && (lits & hdplan::kLitName), lv = has && (lits & hdplan::kLitValue);
-  const uint32_t nlen = ln ? m - a : 0u;
-  wave_copy(ln, frm, frm_cap, a, nlen, out, out_cap, at + nb, lane);
-  wave_copy(lv, frm, frm_cap, m, lv ? e - m : 0u, out, out_cap, at + nb + nlen, lane);
+  const uint32_t nlen = ln ? m - a : 0u, vlen = lv ? e - m : 0u;
+  const Span framed = {frm, frm_cap};  // (a pass for the names, a pass for the values)
+  hdtable::wave_copy(framed, nlen != 0u, Ref{a, nlen}, at + nb, out, out_cap, lane);
+  hdtable::wave_copy(framed, vlen != 0u, Ref{m, vlen}, at + nb + nlen, out, out_cap, lane);
 }
 
 __global__ __launch_bounds__(PL_WG) void k_commit(Stores s, const uint32_t *__restrict__ out_totals,
@@ -488,66 +453,11 @@ __global__ __launch_bounds__(PL_WG) void k_commit(Stores s, const uint32_t *__re
                                                   Entry *ring, uint32_t *__restrict__ ring_key, uint8_t *store,
                                                   uint32_t table_bytes) {
   if (out_totals[2]) return;
-  const uint32_t c = blockIdx.x, lane = threadIdx.x;
-  const Left l = left[c];
-  if (!l.walked) return;
-  const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
-  Entry *cring = ring + (size_t)c * slots;
-  const Entry *cfresh = fresh + (size_t)c * slots;
-  const Conn after = hdreplay::committed_conn(l.h, l.nnew, l.nold, mask);
-  const uint32_t cur_off = (2u * c + (l.h.cur & 1u)) * table_bytes;
-  uint8_t *to = store + (size_t)(2u * c + after.cur) * table_bytes;
-  const uint32_t count = min(after.count, slots), head = after.head;
-  // (hd_replay.hip's k_commit: an entry that stays keeps its slot, and its key)
-  uint32_t run = 0;
-  for (uint32_t i0 = 0; i0 < count; i0 += 64u) {
-    const uint32_t i = i0 + lane;
-    const bool live = i < count;
-    Entry e = {};
-    if (live) {
-      if (i < l.nnew) {
-        e = cfresh[(l.nhead + i) & mask];
-        ring_key[(size_t)c * slots + ((head + i) & mask)] = fresh_key[(size_t)c * slots + ((l.nhead + i) & mask)];
-      } else {
-        e = cring[(l.h.head + (i - l.nnew)) & mask];
-        e.name.off += cur_off;
-        e.value.off += cur_off;
-      }
-    }
-    const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
-    const bool ok = live && ref_ok(s, e.name) && ref_ok(s, e.value);
-    const uint32_t len = ok ? nl + vl : 0u;
-    uint32_t inc = len;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t v = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += v;
-    }
-    const uint32_t at = run + inc - len;
-    const bool fits = ok && (uint64_t)at + len <= table_bytes;
-    // the entries that fit, one after the other, the lanes on consecutive bytes
-    uint64_t m = __ballot(fits);
-    while (m) {
-      const int w = __builtin_ctzll(m);
-      m &= m - 1ull;
-      const Ref wn = {(uint32_t)__builtin_amdgcn_readlane((int)e.name.off, w),
-                      (uint32_t)__builtin_amdgcn_readlane((int)e.name.ls, w)};
-      const Ref wv = {(uint32_t)__builtin_amdgcn_readlane((int)e.value.off, w),
-                      (uint32_t)__builtin_amdgcn_readlane((int)e.value.ls, w)};
-      const uint32_t wat = (uint32_t)__builtin_amdgcn_readlane((int)at, w);
-      const uint32_t wnl = hdreplay::ref_len(wn), wvl = hdreplay::ref_len(wv);
-      const uint8_t *nsrc = hdplan::ref_ptr(s.by, wn), *vsrc = hdplan::ref_ptr(s.by, wv);
-      for (uint32_t b = lane; b < wnl; b += 64u) to[wat + b] = nsrc[b];
-      for (uint32_t b = lane; b < wvl; b += 64u) to[wat + wnl + b] = vsrc[b];
-    }
-    if (live) cring[(head + i) & mask] = hdreplay::committed_entry(at, fits ? nl : 0u, fits ? vl : 0u);
-    run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-  }
-  if (lane == 0u) hdr[c] = after;
+  hdtable::commit<true>(s, blockIdx.x, threadIdx.x, left, fresh, fresh_key, hdr, ring, ring_key, store, table_bytes);
 }
 
 using hdhost::clamp32;
-bool table_bytes_ok(uint32_t tb) { return tb >= 4096u && (tb & (tb - 1u)) == 0u; }
+using hdreplay::table_bytes_ok;
 
 // a string of the arena, or the empty one (the kernel's rule)
 void fit_string(uint32_t *off, uint32_t *len, size_t arena_bytes) {
@@ -560,79 +470,38 @@ extern "C" {
 
 int nghttp2_amd_hd_dev_deflaters_new(nghttp2_amd_hd_dev_deflaters **set_ptr, uint32_t nconn, uint32_t table_bytes,
                                      const uint32_t *deflate_max, void *stream) {
-  if (!set_ptr || nconn == 0 || !table_bytes_ok(table_bytes) || (uint64_t)nconn * 2u * table_bytes > 0xFFFFFFFFull)
-    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  if (!hdtable::set_args_ok(set_ptr, nconn, table_bytes)) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   std::vector<Conn> init(nconn);
   for (uint32_t c = 0; c < nconn; ++c) {
     const uint32_t dm = deflate_max ? deflate_max[c] : hdreplay::kDefaultMax;
     if (dm > table_bytes) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
     hdplan::conn_init(&init[c], dm);
   }
-  nghttp2_amd_hd_dev_deflaters *s = new (std::nothrow) nghttp2_amd_hd_dev_deflaters();
-  if (!s) return NGHTTP2_AMD_ERR_NOMEM;
-  s->nconn = nconn;
-  s->table_bytes = table_bytes;
-  const size_t slots = table_bytes / hdreplay::kOverhead;
-  if (hipMalloc((void **)&s->hdr, (size_t)nconn * sizeof(Conn)) != hipSuccess ||
-      hipMalloc((void **)&s->ring, (size_t)nconn * slots * sizeof(Entry)) != hipSuccess ||
-      hipMalloc((void **)&s->key, (size_t)nconn * slots * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void **)&s->store, (size_t)nconn * 2u * table_bytes) != hipSuccess) {
-    nghttp2_amd_hd_dev_deflaters_del(s);
-    return NGHTTP2_AMD_ERR_NOMEM;
-  }
+  nghttp2_amd_hd_dev_deflaters *s = nullptr;
+  const int rv = hdtable::set_new(&s, nconn, table_bytes, true);
+  if (rv) return rv;
   // (the headers come from host memory that ends with this call: the copy is waited for)
   hipError_t e = hipMemcpyAsync(s->hdr, init.data(), (size_t)nconn * sizeof(Conn), hipMemcpyHostToDevice,
                                 (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
   if (e != hipSuccess) {
-    nghttp2_amd_hd_dev_deflaters_del(s);
+    hdtable::set_del(s);
     return hdhost::hip_rv(e);
   }
   *set_ptr = s;
   return 0;
 }
 
-void nghttp2_amd_hd_dev_deflaters_del(nghttp2_amd_hd_dev_deflaters *set) {
-  if (!set) return;
-  if (set->hdr) (void)hipFree(set->hdr);
-  if (set->ring) (void)hipFree(set->ring);
-  if (set->key) (void)hipFree(set->key);
-  if (set->store) (void)hipFree(set->store);
-  delete set;
-}
+void nghttp2_amd_hd_dev_deflaters_del(nghttp2_amd_hd_dev_deflaters *set) { hdtable::set_del(set); }
 
 int nghttp2_amd_hd_dev_deflaters_change_table_size(nghttp2_amd_hd_dev_deflaters *set, const uint32_t *conn,
                                                    const uint32_t *value, int32_t *rv, uint32_t n, void *stream) {
-  if (n == 0) return 0;
-  if (!set || !conn || !value || !rv) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_change_size, dim3((n + CS_WG - 1u) / CS_WG), dim3(CS_WG), 0, (hipStream_t)stream, set->hdr,
-                     (const Entry *)set->ring, set->nconn, set->table_bytes, conn, value, rv, n);
-  return hdhost::hip_rv(hipGetLastError());
+  return hdtable::set_change_size<ChangeSize>(set, conn, value, rv, n, stream);
 }
 
 int nghttp2_amd_hd_dev_deflaters_read(nghttp2_amd_hd_dev_deflaters *set, uint32_t conn, nghttp2_amd_hd_dev_conn *hdr,
                                       uint32_t *entries, uint8_t *bytes, void *stream) {
-  if (!set || conn >= set->nconn || !hdr || !entries || !bytes) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t tb = set->table_bytes, slots = tb / hdreplay::kOverhead;
-  std::vector<Entry> ring(slots);
-  hipError_t e = hipMemcpyAsync(hdr, set->hdr + conn, sizeof(Conn), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(ring.data(), set->ring + (size_t)conn * slots, slots * sizeof(Entry), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(bytes, set->store + (size_t)(2u * conn + (hdr->cur & 1u)) * tb, tb, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hdhost::hip_rv(e);
-  if (hdr->count > slots) return NGHTTP2_AMD_ERR_FATAL;
-  for (uint32_t i = 0; i < hdr->count; ++i) {
-    const Entry d = ring[(hdr->head + i) & (slots - 1u)];
-    entries[4 * i + 0] = d.name.off;
-    entries[4 * i + 1] = hdreplay::ref_len(d.name);
-    entries[4 * i + 2] = d.value.off;
-    entries[4 * i + 3] = hdreplay::ref_len(d.value);
-  }
-  return 0;
+  return hdtable::set_read(set, conn, hdr, entries, bytes, stream);
 }
 
 size_t nghttp2_amd_hd_dev_deflate_workspace_size(uint32_t nconn, uint32_t table_bytes, size_t nva_cap,
@@ -723,7 +592,7 @@ int nghttp2_amd_hd_deflate_plan_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, 
       (block_nv_off[n] && (!nva || !arena || !recs)))
     return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   Entry *ring = (Entry *)ring_;
-  const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
+  const uint32_t slots = table_bytes / hdreplay::kOverhead;
   std::vector<Entry> fresh(slots);
   std::vector<uint32_t> fresh_key(slots);
   Table t;
@@ -748,20 +617,8 @@ int nghttp2_amd_hd_deflate_plan_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, 
       recs[i].reserved = 0u;
     }
   }
-  // the commit: the live entries' bytes back to back into the other buffer
-  const Conn after = hdreplay::committed_conn(t.h, t.nnew, t.nold, mask);
-  uint8_t *to = store + (size_t)after.cur * table_bytes;
-  for (uint32_t i = 0; i < t.nnew; ++i) keys[(after.head + i) & mask] = fresh_key[(t.nhead + i) & mask];
-  uint32_t at = 0;
-  for (uint32_t i = 0; i < after.count; ++i) {
-    const Entry e = hdreplay::table_get(t, i);
-    const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
-    if (nl) memcpy(to + at, hdplan::ref_ptr(by, e.name), nl);
-    if (vl) memcpy(to + at + nl, hdplan::ref_ptr(by, e.value), vl);
-    ring[(after.head + i) & mask] = hdreplay::committed_entry(at, nl, vl);
-    at += nl + vl;
-  }
-  *hdr = after;
+  *hdr = hdreplay::commit_host(t, ring, store, table_bytes, [&by](Ref r) { return hdplan::ref_ptr(by, r); }, keys,
+                               fresh_key.data());
   return 0;
 }
 

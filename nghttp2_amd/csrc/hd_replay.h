@@ -27,12 +27,14 @@
 // (k_replay, one lane per connection; k_change_size), and with the walk what
 // both sides do around it (at the end of this file): a block's first_is_size,
 // out_totals, a field's record, the header and descriptors a commit leaves.
-// How bytes are copied is each side's own.  Plain C++17, no HIP.
+// The host's commit and the read-out of a ring close the file; the device's
+// commit is hd_devtable.h's.  Plain C++17, no HIP.
 #ifndef NGHTTP2_AMD_HD_REPLAY_H
 #define NGHTTP2_AMD_HD_REPLAY_H
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/nghttp2_amd_hd.h"
 #include "hd_parse.h"
@@ -53,6 +55,8 @@ constexpr uint32_t kExpectSize = NGHTTP2_AMD_HD_DEV_EXPECT_SIZE, kBad = NGHTTP2_
                    kMidBlock = NGHTTP2_AMD_HD_DEV_MID_BLOCK;
 constexpr uint32_t kOverhead = hdhost::kEntryOverhead;
 constexpr uint32_t kDefaultMax = 4096;  // NGHTTP2_HD_DEFAULT_MAX_BUFFER_SIZE
+// a set's table_bytes: a power of two, 4096 or more
+inline bool table_bytes_ok(uint32_t tb) { return tb >= 4096u && (tb & (tb - 1u)) == 0u; }
 
 enum : uint32_t { SRC_STATIC = 0, SRC_WIRE = 1, SRC_POOL = 2, SRC_TABLE = 3 };
 
@@ -321,6 +325,46 @@ HDREPLAY_FN Conn committed_conn(const Conn &h, uint32_t nnew, uint32_t nold, uin
 }
 HDREPLAY_FN Entry committed_entry(uint32_t at, uint32_t nl, uint32_t vl) {
   return Entry{make_ref(SRC_TABLE, at, nl), make_ref(SRC_TABLE, at + nl, vl)};
+}
+
+// The commit on the host, after a walk over t: the live entries' bytes back
+// to back into the other buffer of `store` (the connection's two buffers of
+// table_bytes), their descriptors into `ring` (the ring t reads: an entry that
+// stays keeps its slot, a fresh one goes to a slot no live entry has), and
+// with keys the keys of the entries that entered from fresh_key to ring_key.
+// bytes_of(Ref) is where a Ref's bytes lie.  Returns the header after.
+template <class BytesOf>
+inline Conn commit_host(const Table &t, Entry *ring, uint8_t *store, uint32_t table_bytes, BytesOf &&bytes_of,
+                        uint32_t *ring_key = nullptr, const uint32_t *fresh_key = nullptr) {
+  const Conn after = committed_conn(t.h, t.nnew, t.nold, t.mask);
+  uint8_t *to = store + (size_t)after.cur * table_bytes;
+  if (ring_key)
+    for (uint32_t i = 0; i < t.nnew; ++i) ring_key[(after.head + i) & t.mask] = fresh_key[(t.nhead + i) & t.mask];
+  uint32_t at = 0;
+  for (uint32_t i = 0; i < after.count; ++i) {
+    const Entry e = table_get(t, i);
+    const uint32_t nl = ref_len(e.name), vl = ref_len(e.value);
+    if (nl) memcpy(to + at, bytes_of(e.name), nl);
+    if (vl) memcpy(to + at + nl, bytes_of(e.value), vl);
+    ring[(after.head + i) & t.mask] = committed_entry(at, nl, vl);
+    at += nl + vl;
+  }
+  return after;
+}
+
+// A ring read out: the live entries, newest first, entry i's name offset,
+// name length, value offset, value length into entries[4 i ..].  False, and
+// nothing written, for a header that counts more entries than the ring has.
+inline bool ring_entries(const Conn &h, const Entry *ring, uint32_t slots, uint32_t *entries) {
+  if (h.count > slots) return false;
+  for (uint32_t i = 0; i < h.count; ++i) {
+    const Entry d = ring[(h.head + i) & (slots - 1u)];
+    entries[4 * i + 0] = d.name.off;
+    entries[4 * i + 1] = ref_len(d.name);
+    entries[4 * i + 2] = d.value.off;
+    entries[4 * i + 3] = ref_len(d.value);
+  }
+  return true;
 }
 
 }  // namespace hdreplay

@@ -3,7 +3,10 @@
 // Reference: the table half of nghttp2_hd_inflate_hd_nv (hd_replay.h, the one
 // statement of the walk, shared with the host twin below).  A set of decoding
 // contexts lives in device memory: per connection a 32-byte header, a ring of
-// table_bytes / 32 entry descriptors and two byte stores of table_bytes.
+// table_bytes / 32 entry descriptors and two byte stores of table_bytes.  The
+// set (its allocation, read-back and change of a table size), the wave's copy
+// of byte runs and the commit are hd_devtable.h's, shared with the device
+// deflaters; the host's commit and the ring's read-out are hd_replay.h's.
 //
 // nghttp2_amd_hd_dev_inflate_blocks, one clear of 2 (n + 1) counters and four
 // launches behind parse -> gather -> decode:
@@ -20,30 +23,23 @@
 //                  field's nghttp2_amd_hd_nv, then the wave copies the fields'
 //                  name, NUL, value, NUL one after the other with its lanes
 //                  on consecutive bytes (k_gather's shape).
-//   k_commit       a wave per connection that had blocks: the live entries'
-//                  bytes go back to back into the connection's other store
-//                  buffer, their descriptors become table references, and the
-//                  header is written back with the current-buffer bit flipped.
+//   k_commit       a wave per connection that had blocks: hdtable::commit
+//                  over the four stores.
 // With an overflow bit in out_totals[2], k_emit and k_commit do nothing: no
 // field is written and every table is as before the call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
 #include "../../include/nghttp2_amd_hd.h"
+#include "hd_devtable.h"
 #include "hd_host.h"
 #include "hd_replay.h"
 #include "hd_scan.h"
 
-struct nghttp2_amd_hd_dev_inflaters {
-  uint32_t nconn, table_bytes;
-  hdreplay::Conn *hdr;    // [nconn]
-  hdreplay::Entry *ring;  // [nconn][table_bytes / 32]
-  uint8_t *store;         // [nconn][2][table_bytes]
-};
+struct nghttp2_amd_hd_dev_inflaters : hdtable::Set {};  // (key stays null)
 
 namespace {
 
@@ -52,19 +48,13 @@ using hdreplay::Entry;
 using hdreplay::FieldRef;
 using hdreplay::Ref;
 using hdscan::SC_WG;
+using hdtable::Left;
 
-constexpr uint32_t RP_WG = 64;   // k_replay, k_change_size, k_init: one wave, 64 connections
+constexpr uint32_t RP_WG = 64;   // k_replay, k_init: one wave, 64 connections
 constexpr uint32_t EM_WG = 256;  // k_emit: four waves, 64 records each
 constexpr uint32_t CM_WG = 64;   // k_commit: one wave, one connection
 
 __constant__ hdhost::StaticPool d_static = hdhost::kStaticPool;
-
-// What k_replay leaves k_commit for a connection that had blocks.
-struct Left {  // 64 bytes
-  Conn h;
-  uint32_t nnew, nhead, nold, walked;
-  uint32_t pad[4];
-};
 
 // The workspace: blk_count[n + 1], blk_bytes[n + 1] (cleared by the call),
 // left[nconn], fresh[nconn][slots], fref[ops_cap].
@@ -105,22 +95,11 @@ __global__ __launch_bounds__(RP_WG) void k_init(Conn *__restrict__ hdr, uint32_t
   hdr[c] = h;
 }
 
-__global__ __launch_bounds__(RP_WG) void k_change_size(Conn *__restrict__ hdr, const Entry *__restrict__ ring,
-                                                       uint32_t nconn, uint32_t table_bytes,
-                                                       const uint32_t *__restrict__ conn,
-                                                       const uint32_t *__restrict__ value, int32_t *__restrict__ rv,
-                                                       uint32_t n) {
-  const uint32_t i = blockIdx.x * RP_WG + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t c = conn[i];
-  if (c >= nconn) {
-    rv[i] = NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-    return;
+struct ChangeSize {  // hdtable::k_change_size's rule
+  __device__ int operator()(Conn *h, const Entry *ring, uint32_t table_bytes, uint32_t v) const {
+    return hdreplay::change_table_size(h, ring, table_bytes, v);
   }
-  Conn h = hdr[c];
-  rv[i] = hdreplay::change_table_size(&h, ring + (size_t)c * (table_bytes / hdreplay::kOverhead), table_bytes, value[i]);
-  hdr[c] = h;
-}
+};
 
 __global__ __launch_bounds__(RP_WG) void k_replay(
     const Conn *__restrict__ hdr, const Entry *__restrict__ ring, uint32_t nconn, uint32_t table_bytes,
@@ -179,44 +158,29 @@ __global__ __launch_bounds__(SC_WG) void k_replay_scan(const uint32_t *__restric
 }
 
 // The four stores a Ref can name, with their sizes: a Ref that reaches past
-// its store is not read.
+// its store is not read (hdtable::wave_copy's and hdtable::commit's policy).
 struct Stores {
   const uint8_t *base[4];
   uint64_t bytes[4];
-};
-__device__ __forceinline__ bool ref_ok(const Stores &s, Ref r) {
-  const uint32_t src = hdreplay::ref_src(r);  // (selected, not indexed: the struct stays in registers)
-  const uint64_t lim = src == hdreplay::SRC_STATIC ? s.bytes[0]
-                       : src == hdreplay::SRC_WIRE ? s.bytes[1]
-                       : src == hdreplay::SRC_POOL ? s.bytes[2]
-                       : src == hdreplay::SRC_TABLE ? s.bytes[3]
-                                                    : 0u;
-  return (uint64_t)r.off + hdreplay::ref_len(r) <= lim;
-}
-// The wave copies the strings of the lanes with `has`, one after the other,
-// its lanes on consecutive bytes: lane l's is r's bytes to out[d, ...), with a
-// NUL behind it when nul.  Every store is below cap.
-__device__ __forceinline__ void wave_copy(const Stores &s, bool has, Ref r, uint64_t d, uint8_t *out, uint64_t cap,
-                                          bool nul, uint32_t lane) {
-  uint64_t m = __ballot(has);
-  while (m) {
-    const int l = __builtin_ctzll(m);
-    m &= m - 1ull;
-    const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)r.off, l);
-    const uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)r.ls, l);
-    const uint32_t dlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)d, l);
-    const uint32_t dhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(d >> 32), l);
-    const uint64_t to = ((uint64_t)dhi << 32) | dlo;
-    const uint32_t nb = ls & 0xFFFFFFu, src = ls >> 24;
-    const uint8_t *from = (src == hdreplay::SRC_STATIC ? s.base[0]
-                           : src == hdreplay::SRC_WIRE ? s.base[1]
-                           : src == hdreplay::SRC_POOL ? s.base[2]
-                                                       : s.base[3]) + off;
-    for (uint32_t b = lane; b < nb; b += 64u)
-      if (to + b < cap) out[to + b] = from[b];
-    if (nul && lane == 0u && to + nb < cap) out[to + nb] = 0u;
+  __device__ bool ok(Ref r) const {
+    const uint32_t src = hdreplay::ref_src(r);  // (selected, not indexed: the struct stays in registers)
+    const uint64_t lim = src == hdreplay::SRC_STATIC ? bytes[0]
+                         : src == hdreplay::SRC_WIRE ? bytes[1]
+                         : src == hdreplay::SRC_POOL ? bytes[2]
+                         : src == hdreplay::SRC_TABLE ? bytes[3]
+                                                      : 0u;
+    return (uint64_t)r.off + hdreplay::ref_len(r) <= lim;
   }
-}
+  __device__ const uint8_t *ptr(uint32_t off, uint32_t ls) const {
+    const uint32_t src = ls >> 24;
+    return (src == hdreplay::SRC_STATIC ? base[0]
+            : src == hdreplay::SRC_WIRE ? base[1]
+            : src == hdreplay::SRC_POOL ? base[2]
+                                        : base[3]) + off;
+  }
+  __device__ uint32_t len(uint32_t ls) const { return ls & 0xFFFFFFu; }
+  __device__ bool readable(uint32_t, uint32_t) const { return true; }  // (a Ref that is ok)
+};
 
 __global__ __launch_bounds__(EM_WG) void k_emit(Stores stores, const uint32_t *__restrict__ totals,
                                                 const uint32_t *__restrict__ op_off, uint32_t n, uint32_t ops_cap,
@@ -242,16 +206,14 @@ __global__ __launch_bounds__(EM_WG) void k_emit(Stores stores, const uint32_t *_
   uint32_t idx = 0, at = 0;
   if (has) {
     const uint32_t f0 = block_nv_off[fr.block], f1 = block_nv_off[fr.block + 1];
-    has = r >= op_off[fr.block] && r < op_off[fr.block + 1] && fr.ordinal < f1 - f0 && ref_ok(stores, fr.name) &&
-          ref_ok(stores, fr.value);
+    has = r >= op_off[fr.block] && r < op_off[fr.block + 1] && fr.ordinal < f1 - f0 && stores.ok(fr.name) &&
+          stores.ok(fr.value);
     idx = f0 + fr.ordinal;
     at = arena_base[fr.block] + fr.before;
     has = has && idx < nva_cap;
   }
-  const uint32_t nl = hdreplay::ref_len(fr.name);
   if (has) hdreplay::field_nv(fr, at, &nva[idx]);
-  wave_copy(stores, has, fr.name, at, arena, arena_cap, true, lane);
-  wave_copy(stores, has, fr.value, (uint64_t)at + nl + 1u, arena, arena_cap, true, lane);
+  hdtable::wave_copy(stores, has, fr.name, fr.value, (uint64_t)at, arena, (uint64_t)arena_cap, true, lane);
 }
 
 __global__ __launch_bounds__(CM_WG) void k_commit(Stores stores, const uint32_t *__restrict__ totals,
@@ -260,55 +222,12 @@ __global__ __launch_bounds__(CM_WG) void k_commit(Stores stores, const uint32_t 
                                                   Conn *__restrict__ hdr, Entry *ring, uint8_t *store,
                                                   uint32_t table_bytes) {
   if (totals[3] || out_totals[2]) return;
-  const uint32_t c = blockIdx.x, lane = threadIdx.x;
-  const Left l = left[c];
-  if (!l.walked) return;
   stores.base[0] = d_static.bytes;
-  const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
-  Entry *cring = ring + (size_t)c * slots;
-  const Entry *cfresh = fresh + (size_t)c * slots;
-  const Conn after = hdreplay::committed_conn(l.h, l.nnew, l.nold, mask);
-  const uint32_t cur_off = (2u * c + (l.h.cur & 1u)) * table_bytes;
-  uint8_t *to = store + (size_t)(2u * c + after.cur) * table_bytes;
-  const uint32_t count = after.count, head = after.head;
-  // The slots of the entries that stay, ring[h.head + j], are the slots they
-  // end in, head + nnew + j: a lane reads the descriptor it then replaces,
-  // and the fresh entries go in front of them, into slots no live entry has.
-  uint32_t run = 0;
-  for (uint32_t i0 = 0; i0 < count; i0 += 64u) {
-    const uint32_t i = i0 + lane;
-    const bool live = i < count;
-    Entry e = {};
-    if (live) {
-      if (i < l.nnew) {
-        e = cfresh[(l.nhead + i) & mask];
-      } else {
-        e = cring[(l.h.head + (i - l.nnew)) & mask];
-        e.name.off += cur_off;
-        e.value.off += cur_off;
-      }
-    }
-    const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
-    const bool ok = live && ref_ok(stores, e.name) && ref_ok(stores, e.value);
-    const uint32_t len = ok ? nl + vl : 0u;
-    uint32_t inc = len;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t v = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += v;
-    }
-    const uint32_t at = run + inc - len;
-    const bool fits = ok && (uint64_t)at + len <= table_bytes;
-    wave_copy(stores, fits, e.name, at, to, table_bytes, false, lane);
-    wave_copy(stores, fits, e.value, (uint64_t)at + nl, to, table_bytes, false, lane);
-    if (live) cring[(head + i) & mask] = hdreplay::committed_entry(at, fits ? nl : 0u, fits ? vl : 0u);
-    run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-  }
-  if (lane == 0u) hdr[c] = after;
+  hdtable::commit<false>(stores, blockIdx.x, threadIdx.x, left, fresh, nullptr, hdr, ring, nullptr, store, table_bytes);
 }
 
 using hdhost::clamp32;
-bool table_bytes_ok(uint32_t tb) { return tb >= 4096u && (tb & (tb - 1u)) == 0u; }
+using hdreplay::table_bytes_ok;
 
 }  // namespace
 
@@ -316,70 +235,30 @@ extern "C" {
 
 int nghttp2_amd_hd_dev_inflaters_new(nghttp2_amd_hd_dev_inflaters **set_ptr, uint32_t nconn, uint32_t table_bytes,
                                      void *stream) {
-  // (a table reference is a uint32 offset into the set's store allocation)
-  if (!set_ptr || nconn == 0 || !table_bytes_ok(table_bytes) || (uint64_t)nconn * 2u * table_bytes > 0xFFFFFFFFull)
-    return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  nghttp2_amd_hd_dev_inflaters *s = new (std::nothrow) nghttp2_amd_hd_dev_inflaters();
-  if (!s) return NGHTTP2_AMD_ERR_NOMEM;
-  s->nconn = nconn;
-  s->table_bytes = table_bytes;
-  const size_t slots = table_bytes / hdreplay::kOverhead;
-  if (hipMalloc((void **)&s->hdr, (size_t)nconn * sizeof(Conn)) != hipSuccess ||
-      hipMalloc((void **)&s->ring, (size_t)nconn * slots * sizeof(Entry)) != hipSuccess ||
-      hipMalloc((void **)&s->store, (size_t)nconn * 2u * table_bytes) != hipSuccess) {
-    nghttp2_amd_hd_dev_inflaters_del(s);
-    return NGHTTP2_AMD_ERR_NOMEM;
-  }
+  if (!hdtable::set_args_ok(set_ptr, nconn, table_bytes)) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
+  nghttp2_amd_hd_dev_inflaters *s = nullptr;
+  int rv = hdtable::set_new(&s, nconn, table_bytes, false);
+  if (rv) return rv;
   hipLaunchKernelGGL(k_init, dim3((nconn + RP_WG - 1u) / RP_WG), dim3(RP_WG), 0, (hipStream_t)stream, s->hdr, nconn);
-  const int rv = hdhost::hip_rv(hipGetLastError());
+  rv = hdhost::hip_rv(hipGetLastError());
   if (rv) {
-    nghttp2_amd_hd_dev_inflaters_del(s);
+    hdtable::set_del(s);
     return rv;
   }
   *set_ptr = s;
   return 0;
 }
 
-void nghttp2_amd_hd_dev_inflaters_del(nghttp2_amd_hd_dev_inflaters *set) {
-  if (!set) return;
-  if (set->hdr) (void)hipFree(set->hdr);
-  if (set->ring) (void)hipFree(set->ring);
-  if (set->store) (void)hipFree(set->store);
-  delete set;
-}
+void nghttp2_amd_hd_dev_inflaters_del(nghttp2_amd_hd_dev_inflaters *set) { hdtable::set_del(set); }
 
 int nghttp2_amd_hd_dev_inflaters_change_table_size(nghttp2_amd_hd_dev_inflaters *set, const uint32_t *conn,
                                                    const uint32_t *value, int32_t *rv, uint32_t n, void *stream) {
-  if (n == 0) return 0;
-  if (!set || !conn || !value || !rv) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_change_size, dim3((n + RP_WG - 1u) / RP_WG), dim3(RP_WG), 0, (hipStream_t)stream, set->hdr,
-                     (const Entry *)set->ring, set->nconn, set->table_bytes, conn, value, rv, n);
-  return hdhost::hip_rv(hipGetLastError());
+  return hdtable::set_change_size<ChangeSize>(set, conn, value, rv, n, stream);
 }
 
 int nghttp2_amd_hd_dev_inflaters_read(nghttp2_amd_hd_dev_inflaters *set, uint32_t conn, nghttp2_amd_hd_dev_conn *hdr,
                                       uint32_t *entries, uint8_t *bytes, void *stream) {
-  if (!set || conn >= set->nconn || !hdr || !entries || !bytes) return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t tb = set->table_bytes, slots = tb / hdreplay::kOverhead;
-  std::vector<Entry> ring(slots);
-  hipError_t e = hipMemcpyAsync(hdr, set->hdr + conn, sizeof(Conn), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(ring.data(), set->ring + (size_t)conn * slots, slots * sizeof(Entry), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(bytes, set->store + (size_t)(2u * conn + (hdr->cur & 1u)) * tb, tb, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hdhost::hip_rv(e);
-  if (hdr->count > slots) return NGHTTP2_AMD_ERR_FATAL;
-  for (uint32_t i = 0; i < hdr->count; ++i) {
-    const Entry d = ring[(hdr->head + i) & (slots - 1u)];
-    entries[4 * i + 0] = d.name.off;
-    entries[4 * i + 1] = hdreplay::ref_len(d.name);
-    entries[4 * i + 2] = d.value.off;
-    entries[4 * i + 3] = hdreplay::ref_len(d.value);
-  }
-  return 0;
+  return hdtable::set_read(set, conn, hdr, entries, bytes, stream);
 }
 
 size_t nghttp2_amd_hd_dev_inflate_workspace_size(uint32_t nconn, uint32_t table_bytes, size_t ops_cap,
@@ -452,7 +331,7 @@ int nghttp2_amd_hd_replay_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, uint8_
       (nlits && (!dst || !dst_off || !status)) || hdr->count > table_bytes / hdreplay::kOverhead)
     return NGHTTP2_AMD_ERR_INVALID_ARGUMENT;
   Entry *ring = (Entry *)ring_;
-  const uint32_t slots = table_bytes / hdreplay::kOverhead, mask = slots - 1u;
+  const uint32_t slots = table_bytes / hdreplay::kOverhead;
   std::vector<Entry> fresh(slots);
   std::vector<FieldRef> fref(op_off[n] - op_off[0]);
   const uint32_t cur = hdr->cur & 1u;
@@ -488,19 +367,7 @@ int nghttp2_amd_hd_replay_host(nghttp2_amd_hd_dev_conn *hdr, void *ring_, uint8_
     if (nv.value_len) memcpy(arena + nv.value_off, bytes_of(fr.value), nv.value_len);
     arena[nv.value_off + nv.value_len] = 0;
   }
-  // the commit: the live entries' bytes back to back into the other buffer
-  const Conn after = hdreplay::committed_conn(t.h, t.nnew, t.nold, mask);
-  uint8_t *to = store + (size_t)after.cur * table_bytes;
-  uint32_t at = 0;
-  for (uint32_t i = 0; i < after.count; ++i) {
-    const Entry e = hdreplay::table_get(t, i);
-    const uint32_t nl = hdreplay::ref_len(e.name), vl = hdreplay::ref_len(e.value);
-    if (nl) memcpy(to + at, bytes_of(e.name), nl);
-    if (vl) memcpy(to + at + nl, bytes_of(e.value), vl);
-    ring[(after.head + i) & mask] = hdreplay::committed_entry(at, nl, vl);
-    at += nl + vl;
-  }
-  *hdr = after;
+  *hdr = hdreplay::commit_host(t, ring, store, table_bytes, bytes_of);
   return 0;
 }
 

@@ -915,6 +915,19 @@ def _conn_state(hdr, entries, raw):
     return [(raw[a:a + b], raw[c:c + d]) for a, b, c, d in e]
 
 
+def _host_table(h, ring, store, table_bytes):
+    """[(name, value)], most recent first, of a host twin's table: its header
+    h, its ring (uint32 [4 * slots]) and its two store buffers."""
+    slots = table_bytes // 32
+    ring = ring.reshape(-1, 4)
+    raw = store[int(h["cur"]) * table_bytes:][:table_bytes].tobytes()
+    out = []
+    for i in range(int(h["count"])):
+        a, b, c, d = (int(x) for x in ring[(int(h["head"]) + i) % slots])
+        out.append((raw[a:a + (b & 0xFFFFFF)], raw[c:c + (d & 0xFFFFFF)]))
+    return out
+
+
 class HostReplayInflater:
     """One connection of a DeviceInflaters set on the host
     (nghttp2_amd_hd_replay_host; no GPU): the same header, ring and stores,
@@ -979,15 +992,7 @@ class HostReplayInflater:
 
     def table(self):
         """[(name, value)] of the dynamic table, most recent first."""
-        h = self.hdr[0]
-        slots = self.table_bytes // 32
-        ring = self.ring.reshape(-1, 4)
-        raw = self.store[int(h["cur"]) * self.table_bytes:][:self.table_bytes].tobytes()
-        out = []
-        for i in range(int(h["count"])):
-            a, b, c, d = (int(x) for x in ring[(int(h["head"]) + i) % slots])
-            out.append((raw[a:a + (b & 0xFFFFFF)], raw[c:c + (d & 0xFFFFFF)]))
-        return out
+        return _host_table(self.hdr[0], self.ring, self.store, self.table_bytes)
 
     def table_size(self):
         return int(self.hdr[0]["size"])
@@ -1017,40 +1022,44 @@ ReplayedBlocks = collections.namedtuple(
 DEV_FIELDS_NOT_REPLAYED, DEV_FIELDS_ARENA_SHORT = 0x1, 0x2
 
 
-class DeviceInflaters:
-    """nconn HPACK decoding contexts in device memory
-    (nghttp2_amd_hd_dev_inflaters): the end of the chain parse -> gather ->
-    decode_auto for wire that lies on the device.  table_bytes is the
-    capacity per connection (a power of two >= 4096): an insertion the HPACK
-    maximum admits and the store cannot hold ends its block with
-    NGHTTP2_ERR_NOMEM.  Calls on one set are ordered by their stream."""
+class _DeviceSet:
+    """What the two sets of contexts in device memory share: the handle, and
+    a connection's table changed in size and read back.  _PREFIX names the
+    set's C functions: nghttp2_amd_hd_<_PREFIX>_new, _del, _change_table_size
+    and _read."""
+    _PREFIX = None
 
-    def __init__(self, nconn, table_bytes=4096, device=None, stream=None):
+    def _call(self, name, *args):
+        name = "%s_%s" % (self._PREFIX, name)
+        _check(getattr(self.L, "nghttp2_amd_hd_" + name)(*args), name)
+
+    def _new(self, L, nconn, table_bytes, device, stream, *args):
+        """The set on `device`; args go between table_bytes and the stream."""
         import torch
         self.torch = torch
         self.device = torch.device(device if device is not None else "cuda")
-        self.L = _replay_lib()
+        self.L = L
         self.nconn, self.table_bytes = int(nconn), int(table_bytes)
-        self._ws = self._fields_ws = None
         p = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(self.L.nghttp2_amd_hd_dev_inflaters_new(ctypes.byref(p), self.nconn, self.table_bytes,
-                                                           _stream(stream)), "dev_inflaters_new")
+            self._call("new", ctypes.byref(p), self.nconn, self.table_bytes, *args, _stream(stream))
         self.p = p
 
     def __del__(self):
         if getattr(self, "p", None):
             self.torch.cuda.synchronize(self.device)
-            self.L.nghttp2_amd_hd_dev_inflaters_del(self.p)
+            getattr(self.L, "nghttp2_amd_hd_%s_del" % self._PREFIX)(self.p)
             self.p = None
 
     def _dev(self, a, dtype):
         return self.torch.from_numpy(np.ascontiguousarray(a, dtype).view(np.int32)).to(self.device)
 
     def change_table_size(self, conns, values, stream=None):
-        """nghttp2_hd_inflate_change_table_size for connection conns[i] with
-        values[i]; a connection appears at most once.  Returns the rv's as a
-        device int32 tensor (0 or NGHTTP2_ERR_INVALID_STATE)."""
+        """nghttp2_hd_inflate_change_table_size (the inflaters) or
+        nghttp2_hd_deflate_change_table_size (the deflaters) for connection
+        conns[i] with values[i]; a connection appears at most once.  Returns
+        the rv's as a device int32 tensor: 0, or for an inflater in the middle
+        of a block NGHTTP2_ERR_INVALID_STATE."""
         conns = [int(c) for c in conns]
         if len(set(conns)) != len(conns):
             raise ValueError("change_table_size: a connection appears more than once")
@@ -1061,17 +1070,14 @@ class DeviceInflaters:
         if n:
             c = self._dev(conns, np.uint32)
             v = self._dev([int(x) for x in values], np.uint32)
-            _check(self.L.nghttp2_amd_hd_dev_inflaters_change_table_size(self.p, _p(c), _p(v), _p(rv), n,
-                                                                         _stream(stream)),
-                   "dev_inflaters_change_table_size")
+            self._call("change_table_size", self.p, _p(c), _p(v), _p(rv), n, _stream(stream))
         return rv[:n]
 
     def _read(self, c, stream=None):
         hdr = np.zeros(1, DEV_CONN_DTYPE)
         ent = np.zeros(self.table_bytes // 32 * 4, np.uint32)
         raw = np.zeros(self.table_bytes, np.uint8)
-        _check(self.L.nghttp2_amd_hd_dev_inflaters_read(self.p, int(c), hdr.ctypes.data, ent.ctypes.data,
-                                                        raw.ctypes.data, _stream(stream)), "dev_inflaters_read")
+        self._call("read", self.p, int(c), hdr.ctypes.data, ent.ctypes.data, raw.ctypes.data, _stream(stream))
         return hdr[0], ent, raw.tobytes()
 
     def table(self, c, stream=None):
@@ -1085,13 +1091,6 @@ class DeviceInflaters:
     def table_max(self, c, stream=None):
         return int(self._read(c, stream)[0]["max"])
 
-    def state(self, c, stream=None):
-        """(table, size, max, (expect_size, bad, mid_block)) in one read."""
-        h, ent, raw = self._read(c, stream)
-        f = int(h["flags"])
-        return (_conn_state(h, ent, raw), int(h["size"]), int(h["max"]),
-                (bool(f & DEV_EXPECT_SIZE), bool(f & DEV_BAD), bool(f & DEV_MID_BLOCK)))
-
     def csr(self, conn_of_block):
         """conn_blk_off[nconn+1], conn_blk[n] (device int32 tensors) from the
         connection of every block: a stable sort, so a connection's blocks
@@ -1103,6 +1102,28 @@ class DeviceInflaters:
         off = np.zeros(self.nconn + 1, np.uint32)
         np.cumsum(np.bincount(conn, minlength=self.nconn), out=off[1:])
         return self._dev(off, np.uint32), self._dev(order if len(order) else [0], np.uint32)
+
+
+class DeviceInflaters(_DeviceSet):
+    """nconn HPACK decoding contexts in device memory
+    (nghttp2_amd_hd_dev_inflaters): the end of the chain parse -> gather ->
+    decode_auto for wire that lies on the device.  table_bytes is the
+    capacity per connection (a power of two >= 4096): an insertion the HPACK
+    maximum admits and the store cannot hold ends its block with
+    NGHTTP2_ERR_NOMEM.  Calls on one set are ordered by their stream."""
+
+    _PREFIX = "dev_inflaters"
+
+    def __init__(self, nconn, table_bytes=4096, device=None, stream=None):
+        self._ws = self._fields_ws = None
+        self._new(_replay_lib(), nconn, table_bytes, device, stream)
+
+    def state(self, c, stream=None):
+        """(table, size, max, (expect_size, bad, mid_block)) in one read."""
+        h, ent, raw = self._read(c, stream)
+        f = int(h["flags"])
+        return (_conn_state(h, ent, raw), int(h["size"]), int(h["max"]),
+                (bool(f & DEV_EXPECT_SIZE), bool(f & DEV_BAD), bool(f & DEV_MID_BLOCK)))
 
     def fields_totals(self, stream=None):
         """The totals word of the last call with checks, tokens or http
@@ -1557,15 +1578,7 @@ class HostDeflatePlanner:
 
     def table(self):
         """[(name, value)] of the dynamic table, most recent first."""
-        h = self.hdr[0]
-        slots = self.table_bytes // 32
-        ring = self.ring.reshape(-1, 4)
-        raw = self.store[int(h["cur"]) * self.table_bytes:][:self.table_bytes].tobytes()
-        out = []
-        for i in range(int(h["count"])):
-            a, b, c, d = (int(x) for x in ring[(int(h["head"]) + i) % slots])
-            out.append((raw[a:a + (b & 0xFFFFFF)], raw[c:c + (d & 0xFFFFFF)]))
-        return out
+        return _host_table(self.hdr[0], self.ring, self.store, self.table_bytes)
 
     def table_size(self):
         return int(self.hdr[0]["size"])
@@ -1577,7 +1590,7 @@ class HostDeflatePlanner:
         return self.table(), self.table_size(), self.table_max()
 
 
-class DeviceDeflaters:
+class DeviceDeflaters(_DeviceSet):
     """nconn HPACK encoding contexts in device memory
     (nghttp2_amd_hd_dev_deflaters): header lists that lie on the device --
     a ReplayedBlocks of DeviceInflaters, or packed (nva, arena, block_nv_off)
@@ -1585,72 +1598,17 @@ class DeviceDeflaters:
     connection, a sequence of nconn, or None for 4096; each at most
     table_bytes.  Calls on one set are ordered by their stream."""
 
+    _PREFIX = "dev_deflaters"
+
     def __init__(self, nconn, table_bytes=4096, deflate_max=None, device=None, stream=None):
-        import torch
-        self.torch = torch
-        self.device = torch.device(device if device is not None else "cuda")
-        self.L = _dev_deflate_lib()
-        self.nconn, self.table_bytes = int(nconn), int(table_bytes)
         self._ws = None
         dm = None
         if deflate_max is not None:
-            dm = np.full(self.nconn, deflate_max, np.uint32) if np.isscalar(deflate_max) else \
+            dm = np.full(int(nconn), deflate_max, np.uint32) if np.isscalar(deflate_max) else \
                 np.ascontiguousarray(deflate_max, np.uint32)
-            if len(dm) != self.nconn:
+            if len(dm) != int(nconn):
                 raise ValueError("deflate_max: one value per connection")
-        p = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.L.nghttp2_amd_hd_dev_deflaters_new(ctypes.byref(p), self.nconn, self.table_bytes,
-                                                           dm.ctypes.data if dm is not None else None,
-                                                           _stream(stream)), "dev_deflaters_new")
-        self.p = p
-
-    def __del__(self):
-        if getattr(self, "p", None):
-            self.torch.cuda.synchronize(self.device)
-            self.L.nghttp2_amd_hd_dev_deflaters_del(self.p)
-            self.p = None
-
-    _dev = DeviceInflaters._dev
-    csr = DeviceInflaters.csr
-
-    def change_table_size(self, conns, values, stream=None):
-        """nghttp2_hd_deflate_change_table_size for connection conns[i] with
-        values[i]; a connection appears at most once.  Returns the rv's as a
-        device int32 tensor (all 0)."""
-        conns = [int(c) for c in conns]
-        if len(set(conns)) != len(conns):
-            raise ValueError("change_table_size: a connection appears more than once")
-        if any(c < 0 or c >= self.nconn for c in conns):
-            raise ValueError("change_table_size: connection out of range")
-        n = len(conns)
-        rv = self.torch.zeros(max(1, n), dtype=self.torch.int32, device=self.device)
-        if n:
-            c = self._dev(conns, np.uint32)
-            v = self._dev([int(x) for x in values], np.uint32)
-            _check(self.L.nghttp2_amd_hd_dev_deflaters_change_table_size(self.p, _p(c), _p(v), _p(rv), n,
-                                                                         _stream(stream)),
-                   "dev_deflaters_change_table_size")
-        return rv[:n]
-
-    def _read(self, c, stream=None):
-        hdr = np.zeros(1, DEV_CONN_DTYPE)
-        ent = np.zeros(self.table_bytes // 32 * 4, np.uint32)
-        raw = np.zeros(self.table_bytes, np.uint8)
-        _check(self.L.nghttp2_amd_hd_dev_deflaters_read(self.p, int(c), hdr.ctypes.data, ent.ctypes.data,
-                                                        raw.ctypes.data, _stream(stream)), "dev_deflaters_read")
-        return hdr[0], ent, raw.tobytes()
-
-    def table(self, c, stream=None):
-        """[(name, value)] of connection c's dynamic table, most recent first
-        (synchronises the stream)."""
-        return _conn_state(*self._read(c, stream))
-
-    def table_size(self, c, stream=None):
-        return int(self._read(c, stream)[0]["size"])
-
-    def table_max(self, c, stream=None):
-        return int(self._read(c, stream)[0]["max"])
+        self._new(_dev_deflate_lib(), nconn, table_bytes, device, stream, dm.ctypes.data if dm is not None else None)
 
     def state(self, c, stream=None):
         """(table, size, max) in one read."""

@@ -9,8 +9,9 @@
 //
 // Every round builds one connection, walks calls of several blocks over an
 // arena of exactly the fields' bytes (so a read past a string is a read past
-// the allocation), commits what the walk leaves the way the host twin does,
-// and checks the table against a model kept beside it: a deque of strings
+// the allocation), commits what the walk leaves with the host twin's commit
+// (hdreplay::commit_host), and checks the table, read out with
+// hdreplay::ring_entries, against a model kept beside it: a deque of strings
 // with the reference's insertion and eviction, searched by plain comparison.
 #include <stdint.h>
 #include <stdio.h>
@@ -59,6 +60,7 @@ int main(int argc, char **argv) {
     std::vector<Entry> ring(slots), fresh(slots);
     std::vector<uint32_t> keys(slots), fresh_key(slots);
     std::vector<uint8_t> store(2 * tb);
+    std::vector<uint32_t> entries(4 * slots);
     std::deque<NV> model;
     uint32_t model_size = 0;
     for (int call = 0; call < 6; ++call) {
@@ -149,28 +151,19 @@ int main(int argc, char **argv) {
           CHECK(t.h.size <= t.h.max && t.h.count <= slots);
         }
       }
-      // the commit, as the host twin does it
-      const Conn after = hdreplay::committed_conn(t.h, t.nnew, t.nold, mask);
-      uint8_t *to = store.data() + (size_t)after.cur * tb;
-      for (uint32_t i = 0; i < t.nnew; ++i) keys[(after.head + i) & mask] = fresh_key[(t.nhead + i) & mask];
-      uint32_t at = 0;
-      for (uint32_t i = 0; i < after.count; ++i) {
-        const Entry e = hdreplay::table_get(t, i);
-        const uint32_t nl = ref_len(e.name), vl = ref_len(e.value);
-        CHECK(at + nl + vl <= tb);
-        if (nl) memcpy(to + at, ref_ptr(by, e.name), nl);
-        if (vl) memcpy(to + at + nl, ref_ptr(by, e.value), vl);
-        ring[(after.head + i) & mask] = hdreplay::committed_entry(at, nl, vl);
-        at += nl + vl;
-      }
-      h = after;
+      // the host twin's commit (the model's bytes fit the buffer it writes)
+      uint32_t model_bytes = 0;
+      for (const NV &nv : model) model_bytes += (uint32_t)(nv.first.size() + nv.second.size());
+      CHECK(model_bytes <= tb);
+      h = hdreplay::commit_host(t, ring.data(), store.data(), tb, [&by](Ref r) { return ref_ptr(by, r); }, keys.data(),
+                                fresh_key.data());
       // the committed table is the model, entry for entry, with its keys
-      CHECK(h.count == model.size());
+      CHECK(h.count == model.size() && hdreplay::ring_entries(h, ring.data(), slots, entries.data()));
       for (uint32_t i = 0; i < h.count; ++i) {
-        const Entry e = ring[(h.head + i) & mask];
+        const uint32_t *e = &entries[4 * i];
         const uint8_t *base = store.data() + (size_t)h.cur * tb;
-        CHECK(std::string((const char *)base + e.name.off, ref_len(e.name)) == model[i].first);
-        CHECK(std::string((const char *)base + e.value.off, ref_len(e.value)) == model[i].second);
+        CHECK(std::string((const char *)base + e[0], e[1]) == model[i].first);
+        CHECK(std::string((const char *)base + e[2], e[3]) == model[i].second);
         CHECK(keys[(h.head + i) & mask] == name_hash((const uint8_t *)model[i].first.data(), (uint32_t)model[i].first.size()));
       }
     }

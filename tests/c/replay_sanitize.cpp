@@ -7,9 +7,11 @@
 //       -I nghttp2_amd/csrc -o replay_sanitize tests/c/replay_sanitize.cpp && ./replay_sanitize [rounds] [seed]
 //
 // Every round builds one connection (a small ring, so it wraps and fills),
-// commits what the walk leaves the way the host twin does, and checks that
-// every reference handed out lies inside its store and that the accounted
-// size is the entries' sum.
+// commits what the walk leaves with the host twin's commit
+// (hdreplay::commit_host) over stores of exactly the bytes a reference may
+// name, reads the ring out (hdreplay::ring_entries), and checks that every
+// reference handed out lies inside its store and that the accounted size is
+// the entries' sum.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,11 +42,14 @@ int main(int argc, char **argv) {
   const int rounds = argc > 1 ? atoi(argv[1]) : 2000;
   rng_state = argc > 2 ? strtoull(argv[2], nullptr, 10) | 1u : 1u;
   const uint32_t tb = 4096, slots = tb / kOverhead, wire_bytes = 1u << 12, nlits = 64;
+  const uint32_t pool_bytes = (1u << 16) + 2000u;  // (the furthest a decoded literal below can end)
   uint64_t fields = 0, fails = 0, nomem = 0;
   for (int round = 0; round < rounds; ++round) {
     Conn h;
     conn_init(&h);
     std::vector<Entry> ring(slots), fresh(slots);
+    std::vector<uint8_t> wire(wire_bytes, 'w'), pool(pool_bytes, 'p'), store(2 * tb);
+    std::vector<uint32_t> entries(4 * slots);
     std::vector<uint32_t> dst_off(nlits);
     std::vector<int32_t> status(nlits);
     for (uint32_t k = 0; k < nlits; ++k) {
@@ -128,24 +133,20 @@ int main(int argc, char **argv) {
         CHECK(t.h.count == t.nnew + t.nold && t.h.count <= slots && t.h.size <= tb);
         CHECK(t.h.size <= t.h.max || t.h.count == 0);
       }
-      // the commit, as the host twin does it: the entries' bytes back to back in the other buffer
-      const uint32_t count = t.nnew + t.nold, head = (t.h.head - t.nnew) & t.mask;
+      // the host twin's commit: the entries' bytes back to back in the other buffer
+      const uint8_t *stores[4] = {hdhost::kStaticPool.bytes, wire.data(), pool.data(), store.data()};
+      h = commit_host(t, ring.data(), store.data(), tb, [&](Ref r) { return stores[ref_src(r)] + r.off; });
+      CHECK(h.count == t.nnew + t.nold && h.head == ((t.h.head - t.nnew) & t.mask) && h.cur == (cur ^ 1u));
+      cur = h.cur;
+      CHECK(ring_entries(h, ring.data(), slots, entries.data()));
       uint32_t at = 0, size = 0;
-      for (uint32_t i = 0; i < count; ++i) {
-        const Entry e = table_get(t, i);
-        const uint32_t nl = ref_len(e.name), vl = ref_len(e.value);
-        Entry d;
-        d.name = make_ref(SRC_TABLE, at, nl);
-        d.value = make_ref(SRC_TABLE, at + nl, vl);
-        ring[(head + i) & t.mask] = d;
+      for (uint32_t i = 0; i < h.count; ++i) {
+        const uint32_t nl = entries[4 * i + 1], vl = entries[4 * i + 3];
+        CHECK(entries[4 * i] == at && entries[4 * i + 2] == at + nl);
         at += nl + vl;
         size += nl + vl + kOverhead;
       }
       CHECK(at <= tb && size == t.h.size);
-      h = t.h;
-      h.head = head;
-      h.count = count;
-      h.cur = cur ^= 1u;
     }
   }
   printf("replay_sanitize: ok (%d rounds, %llu fields, %llu failed blocks, %llu NOMEM)\n", rounds,

@@ -22,6 +22,9 @@ def test_fixture_holds_the_cases():
     assert [r[0] for r in GOLDEN["nghttp2_amd_hd_dev_fields_http_workspace_size"]] == \
         [0, 1, 3, 4, 63, 64, 255, 256, 257, 2**31 - 1, 2**31]
     assert [r[0] for r in GOLDEN["nghttp2_amd_hd_parse_blocks_bound.ws_bytes"]] == [0, 1, 3, 4, 64]
+    rows = GOLDEN["nghttp2_amd_hd_dev_deflate_workspace_size"]
+    assert [tuple(r[:5]) for r in rows] == list(itertools.product((1, 2, 65), (4096, 8192), (0, 1, 63, 64, 65),
+                                                                  (0, 31, 32, 33), (1, 64)))
 
 
 def test_sizes_are_the_recorded_ones():
